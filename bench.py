@@ -12,8 +12,12 @@ shadow), counted on the device.
 
     python bench.py [--gpus N --steps K --warmup W]          # N>1: under torch.distributed.run
 
-Prints one JSON line on rank 0. See DESIGN.md §Measurement for the roofline and CPU-baseline
-definitions.
+Prints one JSON line on rank 0. A plain run sets up, warms up, times the K steps and prints the
+headline (value, ms_per_step and the configuration); `--full` goes on to every other leg (the other
+modes over the same frames, moving view, cold frame, strong-scaling shares, end to end, roofline,
+drop-in loop, CPU baseline with the in-run parity check) and reports them in the same line.
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (dump_outputs). See
+DESIGN.md §Measurement for the roofline and CPU-baseline definitions.
 """
 from __future__ import annotations
 
@@ -92,6 +96,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=100)   # ~50 ms of C4 frames: fixed sync costs amortised
     ap.add_argument("--warmup", type=int, default=20)   # (the launch trials run before it: calibration)
     ap.add_argument("--mode", choices=("weak", "strong"), default="weak")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other leg (the other modes over the same frames, moving "
+                         "view, cold frame, strong-scaling shares, end to end, shard path, roofline, drop-in loop, CPU "
+                         "baseline and parity) and report them in the line; without it the run stops at the headline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0: write what the last timed step returned to DIR/<name>.npy (float32; dump_outputs)")
     ap.add_argument("--cpu-sample-every", type=int, default=0,
                     help="CPU baseline: every k-th tile (0: the workload's default, C2 the full frame)")
     ap.add_argument("--cpu-threads", type=int, default=16, help="the GPU box's CPU share (16 per GPU)")
@@ -256,6 +266,7 @@ def main():
             self.pidx = 0          # next path position
             self.rays_acc = 0      # rays of the path views rendered since the last reset
             self.last_pos = 0      # path position of the last rendered frame
+            self.last_bufs = None  # the frame buffers of the last render_call
             # rank 0 un-permutes on a side stream, so the next step's render is not queued behind it
             self.side = torch.cuda.Stream(dev) if (rank == 0 and not frame_path) else None
 
@@ -310,6 +321,7 @@ def main():
                 self.pidx += k
                 self.last_pos = pos[-1]
             scene.render_frames_device(views, TILE, TILE, [b.data_ptr() for b in bufs], bufs[0].numel(), st.cuda_stream)
+            self.last_bufs = bufs
             return bufs[-1]
 
         def step(self, i, k=1):
@@ -468,6 +480,74 @@ def main():
     one_in_flight = in_flight = None
     value_mode = (f"{fpc}_frames_per_call" if fpc > 1 else "") + (f"{'_' if fpc > 1 else ''}{inflight}_in_flight" if inflight > 1 else "")
     value_mode = (value_mode or "one_in_flight") + ("_camera_path" if timed_rays else "")
+    # what the last timed step returned to its caller, kept before any later leg reuses the buffers (--dump-outputs)
+    dumps = None
+    if args.dump_outputs and timed_last is not None:
+        dumps = {"frame": timed_last[-1].cpu().numpy()}
+        if main_run.single and fpc > 1:   # (the last call's frames, each a view of the camera path)
+            dumps["call_frames"] = torch.stack(main_run.last_bufs).view(-1, HEIGHT, WIDTH, 3).cpu().numpy()
+        elif timed_last.shape[0] > 1:   # (N > 1: the step's assembled frames on rank 0)
+            dumps["call_frames"] = timed_last.cpu().numpy()
+
+    def headline():
+        """The result line of a plain run; --full adds its legs' figures to it."""
+        total_rays = timed_rays if timed_rays else rays_per_step * args.steps
+        return {
+            "metric": METRIC,
+            "value": round(total_rays / elapsed / 1e6, 4),
+            "unit": "Mrays/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+            "higher_is_better": True,
+            "scaling": "weak" if args.mode == "weak" else "strong",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic",
+            "full": args.full,
+            "config": {
+                "workload": wl["desc"],
+                "frames_per_step": plan.frames // kstep,
+                "steps_per_call": kstep if world > 1 else None,
+                "width": WIDTH, "height": HEIGHT, "pf": PF, "max_lvl": MAX_LVL, "lights": [list(l) for l in LIGHTS],
+                "triangles": nt, "vertices": nv, "tile": TILE,
+                "parallelism": f"tile-shard{world}",
+                "path": ("rt_render_frame_device" if main_run.single else
+                         "rt_render_frames_sharded (library RCCL gather + un-permute)" if rtcomm is not None else
+                         "rt_render_tiles_device + gloo host-staged gather (rehearsal) + rt_assemble_tiles_device"
+                         if args.rehearse else
+                         "rt_render_tiles_device + RCCL gather (torch.distributed) + rt_assemble_tiles_device"),
+                "rays_per_step": int(rays_per_step),
+                "rays_by_kind_per_step": {"primary": rays_by_kind[0], "secondary": rays_by_kind[1], "shadow": rays_by_kind[2]},
+                "frame_ms_per_gpu": round(elapsed / args.steps * 1e3, 3),
+                "frames_in_flight": inflight,
+                "value_mode": value_mode,
+                "calibration_frames": calib,
+                "frames_per_call": fpc,
+                "camera_path": path_what,
+                "scene_load_s": round(t_load, 3), "scene_gen_s": round(t_gen, 3),
+            },
+            "accel": {"mode": args.accel, "bvh": bvh_info},
+        }
+
+    def finish(result):
+        """Rank 0 writes the outputs asked for and prints the line; every rank leaves its process group."""
+        if rank == 0 and dumps is not None:
+            dump_outputs(args.dump_outputs, dumps)
+        if rank == 0 and args.ppm and timed_last is not None:
+            R.write_ppm(args.ppm, timed_last[0].cpu().numpy())
+        if rtcomm is not None:
+            rtcomm.close()
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+
+    if not args.full:   # a plain run: the headline alone
+        finish(headline() if rank == 0 else None)
+        return
     # (the modes beside the headline time at least LEG_STEPS frames, whatever --steps the headline takes: a run of
     # 20 frames one at a time reads ~6% above the steady state, its first launch and last sync unamortised)
     leg_steps, leg_warm = max(args.steps, LEG_STEPS), max(args.warmup, 20)
@@ -653,8 +733,6 @@ def main():
 
     result = None
     if rank == 0:
-        total_rays = timed_rays if timed_rays else rays_per_step * args.steps
-        value = total_rays / elapsed / 1e6
         queries = ch_tests / max(nt, 1)
         per_rank_steps = args.profile_steps * (fpc if main_run.single else kstep)   # frames (of steps) in the profiled launches
         traffic = traffic_src = None
@@ -715,39 +793,10 @@ def main():
                     "bytes_per_launch": traffic, "source": traffic_src,
                     "what": "bytes past the XCD L2s (PMC 2*FETCH_SIZE + WRITE_SIZE, gfx950 correction) / "
                             "average launch time; Infinity Cache hits are included"}
-        result = {
-            "metric": METRIC,
-            "value": round(value, 4),
-            "unit": "Mrays/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "weak" if args.mode == "weak" else "strong",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {
-                "workload": wl["desc"],
-                "frames_per_step": plan.frames // kstep,
-                "steps_per_call": kstep if world > 1 else None,
-                "width": WIDTH, "height": HEIGHT, "pf": PF, "max_lvl": MAX_LVL, "lights": [list(l) for l in LIGHTS],
-                "triangles": nt, "vertices": nv, "tile": TILE,
-                "parallelism": f"tile-shard{world}",
-                "path": ("rt_render_frame_device" if main_run.single else
-                         "rt_render_frames_sharded (library RCCL gather + un-permute)" if rtcomm is not None else
-                         "rt_render_tiles_device + gloo host-staged gather (rehearsal) + rt_assemble_tiles_device"
-                         if args.rehearse else
-                         "rt_render_tiles_device + RCCL gather (torch.distributed) + rt_assemble_tiles_device"),
-                "rays_per_step": int(rays_per_step),
-                "rays_by_kind_per_step": {"primary": rays_by_kind[0], "secondary": rays_by_kind[1], "shadow": rays_by_kind[2]},
-                "frame_ms_per_gpu": round(elapsed / args.steps * 1e3, 3),
-                "frames_in_flight": inflight,
-                "value_mode": value_mode,
+        result = headline()
+        result["config"].update({
                 "value_mode_what": "value/ms_per_step come from the configured mode (--frames-per-call, --inflight); "
                                    "one_in_flight (and in_flight) time the same K frames in the other modes in the same run",
-                "calibration_frames": calib,
                 "calibration_what": "frames rendered one at a time before the warm-up, over the F pipelines of the "
                                     "timed mode in turn, until pipeline 0's launch trials were decided (rt_scene_trials; "
                                     "at most 64 per pipeline), then to the end of the round",
@@ -757,12 +806,10 @@ def main():
                                          "the per-frame throughput time, one_in_flight the frame-after-frame time",
                 "one_in_flight": one_in_flight,
                 "in_flight": in_flight,
-                "frames_per_call": fpc,
                 "frames_per_call_what": "frames rendered by one rt_render_frames_device call: one chain launch whose wave "
                                         "tasks cycle over the frames (the frames overlap on one stream and one hardware "
                                         "queue); with camera_path, consecutive distinct views of the path; ms_per_step = "
                                         "wall clock / frames",
-                "camera_path": path_what,
                 "orbit": orbit,
                 "multi_frame": multi_frame,
                 "first_frame_ms": round(cold_ms, 3) if cold_ms is not None else None,
@@ -771,8 +818,8 @@ def main():
                                     "wave tasks (RT_TUNE_CHAIN_SPLIT 5), median of 3, host wall clock from the call to its render stream's completion (the library's background re-sort for the next frame not waited for)",
                 "launch_trials": trials,
                 "first_frame_screen_order_ms": round(cold_screen_ms, 3) if cold_screen_ms is not None else None,
-                "scene_load_s": round(t_load, 3), "scene_gen_s": round(t_gen, 3),
-            },
+        })
+        result.update({
             "roofline": {
                 "kernel": f"{kname} ({'every chain step: closest-hit, shadow and shade' if kname == 'k_chain' else 'primary + secondary queries'}, accel={args.accel})",
                 "frames_per_launch": fpc,
@@ -810,9 +857,8 @@ def main():
             },
             "roofline_bruteforce": bf,
             "batches": batches,
-            "accel": {"mode": args.accel, "bvh": bvh_info},
             "cpu_baseline": None,
-        }
+        })
         result.update(extra)
         if shares is not None:
             result["strong_shares"] = dict(shares, what="rank r's 1/N share of ONE frame (rt_render_tiles_device, tiles r, "
@@ -829,8 +875,6 @@ def main():
                                                   WIDTH * HEIGHT * 3, shares=shares, t1_pipe_ms=elapsed / args.steps * 1e3)
         if rehearsal is not None:
             result["rehearsal"] = rehearsal
-        if args.ppm and timed_last is not None:
-            R.write_ppm(args.ppm, timed_last[0].cpu().numpy())
 
     # ---- the reference's own caller unchanged: main.cpp's 'r' loop over the source-level drop-in ----
     if rank == 0 and world == 1 and wl.get("dropin") and not args.no_dropin:
@@ -843,13 +887,25 @@ def main():
         if orbit_last is not None:   # the last timed orbit view, on tiles across its sphere region
             result["config"]["orbit"]["parity_vs_cpu"] = orbit_parity(obj, params, orbit_last, wl)
 
-    if rtcomm is not None:
-        rtcomm.close()
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0:
-        print(json.dumps(result), flush=True)
+    finish(result)
+
+
+DUMP_BUDGET = 60 << 20   # bytes of --dump-outputs in all (float32 elements, split evenly over the arrays)
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: each array of `arrays` as directory/<name>.npy in float32. An array that
+    fits its share of DUMP_BUDGET is written whole; of a larger one, the elements at a fixed seeded
+    sample of flat positions (the same positions in every run of the same shapes, in ascending order),
+    so two builds' dumps compare element for element."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_BUDGET // 4 // len(arrays)
+    for name, a in arrays.items():
+        if a.size > share:
+            at = np.sort(np.random.default_rng(0x5EED).integers(0, a.size, size=share))
+            a = a.reshape(-1)[at]
+        np.save(os.path.join(directory, name + ".npy"), a.astype(np.float32))
 
 
 def multiframe_leg(scene, run, cparams, W, H, args, rays_per_frame, dev):

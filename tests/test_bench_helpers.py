@@ -1,7 +1,34 @@
 """bench.py's bookkeeping helpers (CPU): which profiled kernel name is the timed loop's instantiation
 (the roofline's traffic, issue counters and rocprof mean must come from the kernel the headline runs),
 and the strong-scaling model's arithmetic."""
+import numpy as np
+
 import bench
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs writes float32 .npy files: an array within its share of the budget whole, a
+    larger one as the same seeded sample of positions in every run, ascending."""
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 2 * 4 * 1000)   # 1000 float32 elements per array
+    small = np.arange(5 * 7 * 3, dtype=np.uint8).reshape(5, 7, 3)
+    large = (np.arange(4 * 30 * 20 * 3) % 251).astype(np.uint8).reshape(4, 30, 20, 3)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"frame": small, "call_frames": large})
+    frame, sample = np.load(tmp_path / "a" / "frame.npy"), np.load(tmp_path / "a" / "call_frames.npy")
+    assert frame.dtype == np.float32 and np.array_equal(frame, small)
+    assert sample.dtype == np.float32 and sample.shape == (1000,)
+    assert np.array_equal(sample, np.load(tmp_path / "b" / "call_frames.npy"))
+    at = np.sort(np.random.default_rng(0x5EED).integers(0, large.size, size=1000))
+    assert np.array_equal(sample, large.reshape(-1)[at])
+
+
+def test_plain_run_is_the_default(monkeypatch):
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs == "" and a.steps == 3
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
 
 
 def test_timed_instantiation_picks_the_headline_kernel():

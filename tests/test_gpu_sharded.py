@@ -251,7 +251,7 @@ def test_bench_multi_rank_rehearsal(tmp_path, gpu_available):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", "29533", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--rehearse", "--workload", "c2", "--no-cpu", "--no-bf-roofline", "--no-cold",
+           "--warmup", "1", "--full", "--rehearse", "--workload", "c2", "--no-cpu", "--no-bf-roofline", "--no-cold",
            "--no-path-compare", "--frames-per-call", "1"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=180, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
@@ -268,8 +268,8 @@ def test_bench_multi_rank_rehearsal_steps_per_call(tmp_path, gpu_available):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", "29534", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "8",
-           "--warmup", "4", "--frames-per-call", "4", "--rehearse", "--workload", "c2", "--no-cpu", "--no-bf-roofline",
-           "--no-cold", "--no-path-compare"]
+           "--warmup", "4", "--full", "--frames-per-call", "4", "--rehearse", "--workload", "c2", "--no-cpu",
+           "--no-bf-roofline", "--no-cold", "--no-path-compare"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=180, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads(r.stdout.strip().splitlines()[-1])

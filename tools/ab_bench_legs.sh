@@ -7,7 +7,7 @@ cd "$GRAFT_REPO_ROOT"
 TAG=$1; P=$2; shift 2
 for pass in $(seq 1 $P); do
   for V in "$@"; do
-    N=${V%%:*}; X=${V#*:}
+    N=${V%%:*}; X="--full ${V#*:}"   # (the legs are the full line's)
     LIBV=""; case $N in *@*) LIBV=raytracert_amd/ab/lib_${N#*@}.so ;; esac
     R=$(RTAMD_LIB=$LIBV timeout -k 10 300 python bench.py --no-cpu --no-bf-roofline --no-path-compare --no-dropin --no-strong-shares --no-e2e $X 2>gpurun_out/ab_legs_$TAG.err) || { tail -20 gpurun_out/ab_legs_$TAG.err; exit 1; }
     echo "$R" >> gpurun_out/ab_legs_$TAG.jsonl

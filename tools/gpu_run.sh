@@ -6,7 +6,7 @@
 #   strong_c4    strong-scaling shares on one GPU, C4 (tools/strong_probe.py; STRONG_VARIANTS, STRONG_LIB)
 #   strong_c5    the same for C5
 #   phases       per-phase VALU PMC of the four-frame launch (tools/phase_probe.py + tools/phase_summary.py)
-#   bench        python bench.py (driver defaults; BENCH_ARGS extra)
+#   bench        python bench.py (driver defaults: the headline alone; BENCH_ARGS extra, --full for every leg)
 #   pmc          tools/gpu_pmc.sh TAG + summary into profiles/TAG_pmc.json
 #   rocprof      rocprofv3 --kernel-trace --stats of the bench's timed entry point + trace summary
 #   workloads    tools/gpu_workloads.sh TAG (the other BASELINE workloads)
@@ -63,7 +63,7 @@ for STEP in "$@"; do
         for W in ${AB_WORKLOADS:-c4}; do
           for L in ${AB_LIBS:-cur}; do
             LIBV=""; [ "$L" != "cur" ] && LIBV=raytracert_amd/ab/lib_$L.so
-            R=$(RTAMD_LIB=$LIBV timeout -k 10 300 python bench.py --workload $W --no-cpu --no-bf-roofline --no-cold --no-path-compare \
+            R=$(RTAMD_LIB=$LIBV timeout -k 10 300 python bench.py --full --workload $W --no-cpu --no-bf-roofline --no-cold --no-path-compare \
                 --no-dropin --no-strong-shares --no-e2e --orbit-step 0 --no-multi-frame ${AB_ARGS:-} 2>gpurun_out/ab_$TAG.err) || fail ab gpurun_out/ab_$TAG.err
             echo "$R" >> gpurun_out/ab_$TAG.jsonl
             echo "$R" | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); c=d["config"]; b=d.get("batches") or {}; print(sys.argv[1], sys.argv[2], "pass", sys.argv[3], d["ms_per_step"], "ms", "one", (c.get("one_in_flight") or {}).get("ms_per_step"), "in_flight", (c.get("in_flight") or {}).get("ms_per_step"), "chain", d["roofline"]["avg_launch_ms"], "batch max", b.get("max_us"))' $W $L $P
