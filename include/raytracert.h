@@ -157,6 +157,29 @@ int  rt_scene_info(const rt_scene *scene, int32_t *n_vertices, int32_t *n_triang
 int  rt_scene_export(const rt_scene *scene, float *vertices, uint32_t *tri_v, uint32_t *tri_mat,
                      rt_material *materials, float *face_normals);
 int  rt_get_material(const rt_scene *scene, int32_t triangle_index, rt_material *out);
+/* Dynamic geometry (an extension: the reference's mesh is fixed after init, raytracing.cpp:42-76). New
+ * positions for the scene's vertices, xyz = 3 * n_vertices floats with n_vertices the scene's own count;
+ * triangles, materials and texture coordinates stay. After a successful return every entry behaves bit
+ * for bit as on a scene created from the same arrays: intersectMesh's result is the (distance, index)
+ * minimum over accepted triangles (raytracing.cpp:161-192) whatever the tree's shape, so the BVH keeps
+ * its topology and only its boxes are recomputed (a refit; on a device scene by HIP kernels from a
+ * persistent device copy of the vertices). The trees are rebuilt from the new vertices when some
+ * triangle moved between the classes the topology bakes in (in the tree / ill-conditioned and tested by
+ * every query / degenerate and never accepted), or on request (RT_UPDATE_REBUILD: a refitted tree of a
+ * heavily deformed mesh renders the same bytes more slowly). *outcome (may be NULL) says which happened.
+ * The update runs after every render queued on the scene before it and is complete on return. Batch
+ * orders, launch trials and workspaces are kept. RT_E_ARG (scene untouched) for a NULL scene or array, a
+ * wrong vertex count or an unknown mode. */
+#define RT_UPDATE_AUTO      0   /* refit; rebuild only if some triangle changed class */
+#define RT_UPDATE_REBUILD   1   /* always rebuild the trees from the new vertices */
+#define RT_UPDATED_REFIT    0
+#define RT_UPDATED_REBUILT  1
+int  rt_scene_update_vertices(rt_scene *scene, const float *xyz, int32_t n_vertices, int32_t mode, int32_t *outcome);
+/* The same from device memory on the scene's device (e.g. a simulation's output; no host copy unless
+ * the trees are rebuilt). The array must be complete when the call is made: it is read on the scene's
+ * own stream. RT_E_NODEV on a host-only scene. */
+int  rt_scene_update_vertices_device(rt_scene *scene, const void *d_xyz, int32_t n_vertices, int32_t mode,
+                                     int32_t *outcome);
 
 /* ---- hot path ------------------------------------------------------------------------- */
 /* rayIntersectTriangle (raytracing.cpp:99-154) for n independent (ray, triangle) pairs on device

@@ -111,6 +111,16 @@ class RayTracer {
         MyLightPositions.push_back(MyCameraPosition);
     }
 
+    // Extension (the reference's mesh is fixed after init): new positions for MyMesh.vertices, same count
+    // (rt_scene_update_vertices). True when the BVH was refitted, false when it had to be rebuilt; the
+    // scene then renders as one loaded from the new vertices either way.
+    bool updateVertices(const std::vector<Vec3Df> &vertices, bool rebuild = false) {
+        int32_t outcome = RT_UPDATED_REBUILT;
+        check(rt_scene_update_vertices(scene_, vertices.empty() ? nullptr : vertices[0].p, static_cast<int32_t>(vertices.size()),
+                                       rebuild ? RT_UPDATE_REBUILD : RT_UPDATE_AUTO, &outcome));
+        return outcome == RT_UPDATED_REFIT;
+    }
+
     // getMaterial(int), raytracing.cpp:373-376
     Material getMaterial(int index) const {
         rt_material m;

@@ -61,6 +61,8 @@ DEFAULT_SEED = 0x5EED
 LOAD_PARALLEL, LOAD_SEQUENTIAL = 0, 1
 LOAD_TEXCOORDS = 0x10
 WORK_FIELDS = 6
+UPDATE_AUTO, UPDATE_REBUILD = 0, 1      # rt_scene_update_vertices modes
+UPDATED_REFIT, UPDATED_REBUILT = 0, 1   # ... and outcomes
 
 
 class RtParams(C.Structure):
@@ -107,6 +109,8 @@ _SIGNATURES = {
     "rt_scene_destroy": ([_VP], None),
     "rt_scene_info": ([_VP, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)], C.c_int),
     "rt_scene_export": ([_VP, _VP, _VP, _VP, _VP, _VP], C.c_int),
+    "rt_scene_update_vertices": ([_VP, _VP, C.c_int32, C.c_int32, C.POINTER(C.c_int32)], C.c_int),
+    "rt_scene_update_vertices_device": ([_VP, _VP, C.c_int32, C.c_int32, C.POINTER(C.c_int32)], C.c_int),
     "rt_get_material": ([_VP, C.c_int32, C.POINTER(RtMaterial)], C.c_int),
     "rt_ray_intersect_triangle": ([C.c_int32, _VP, _VP, C.c_int32, _VP, _VP], C.c_int),
     "rt_intersect_mesh": ([_VP, _VP, _VP, C.c_int32, _VP, _VP], C.c_int),

@@ -194,6 +194,28 @@ class Scene:
                          illum=m.illum, flags=m.flags) for m in list(mats)[:nm]]
         return dict(vertices=verts, triangles=tri, tri_mat=tmat, materials=mat_list, normals=normals)
 
+    def update_vertices(self, vertices, mode: str = "auto") -> str:
+        """rt_scene_update_vertices: new positions for the scene's vertices (dynamic geometry). `vertices`
+        is a float32 (n, 3) array, or a CUDA torch tensor of that shape on the scene's device, which goes
+        through rt_scene_update_vertices_device with no host copy. mode 'auto' refits the BVH and rebuilds
+        it only if some triangle changed class; 'rebuild' always rebuilds. Returns 'refit' or 'rebuilt';
+        either way the scene then behaves bit for bit as one created from the new vertices."""
+        m = {"auto": _capi.UPDATE_AUTO, "rebuild": _capi.UPDATE_REBUILD}.get(mode, mode)
+        out = C.c_int32(-1)
+        if hasattr(vertices, "data_ptr") and getattr(vertices, "is_cuda", False):
+            import torch
+            if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 3:
+                raise ValueError("update_vertices: a float32 (n, 3) tensor is required")
+            t = vertices.contiguous()
+            torch.cuda.current_stream(t.device).synchronize()   # the library reads it on its own stream
+            check(lib().rt_scene_update_vertices_device(self._h, C.c_void_p(t.data_ptr()), int(t.shape[0]), int(m), C.byref(out)))
+        else:
+            v = np.ascontiguousarray(vertices, np.float32)
+            if v.ndim != 2 or v.shape[1] != 3:
+                raise ValueError("update_vertices: a float32 (n, 3) array is required")
+            check(lib().rt_scene_update_vertices(self._h, _ptr(v), len(v), int(m), C.byref(out)))
+        return "refit" if out.value == _capi.UPDATED_REFIT else "rebuilt"
+
     def texcoords(self) -> tuple[np.ndarray, np.ndarray]:
         """rt_scene_texcoords (a scene loaded with texcoords=True): (texcoords[n, 3] float32 with z = 0,
         tri_t[nt, 3] uint32), Mesh::texcoords and each Triangle::t."""

@@ -568,6 +568,123 @@ int build_bvh(const HostScene &s, const std::vector<TriRec> &recs, HostBvh &out)
     return RT_OK;
 }
 
+// ---- refit (rt_scene_update_vertices) ------------------------------------------------------
+// The traversal's result is the (distance, index) minimum over accepted triangles (top of this file), so
+// any tree whose boxes contain the padded acceptance boxes below them gives the reference's bytes: a
+// refit keeps the topology (child refs, leaf order, always list) and recomputes every box as the exact
+// min/max union of what lies below it. Only a triangle's class (tree / always tested / never accepted)
+// is baked into the topology; a triangle whose class changed cannot be refitted.
+int tri_class(const TriRec &T, const float *v0, const float *v1, const float *v2, float lo[3], float hi[3]) {
+    bool never = false;
+    if (!acceptance_box(T, v0, v1, v2, lo, hi, &never)) return kTriAlways;
+    return never ? kTriNever : kTriTree;
+}
+
+void built_classes(const HostBvh &h, size_t nt, std::vector<uint8_t> &cls) {
+    cls.assign(nt, kTriNever);
+    for (uint32_t t : h.leaf_tris) cls[t] = kTriTree;
+    for (uint32_t t : h.always) cls[t] = kTriAlways;
+}
+
+float scene_m1_of(const float *xyz, size_t nv) {
+    double m1 = 0;
+    for (size_t i = 0; i < nv; ++i)
+        m1 = std::max(m1, std::fabs(double(xyz[3 * i])) + std::fabs(double(xyz[3 * i + 1])) + std::fabs(double(xyz[3 * i + 2])));
+    return static_cast<float>(m1 * (1 + 1e-6));
+}
+
+namespace {
+struct Refitter {
+    const std::vector<Box> &slot;   // padded acceptance box of each leaf slot
+    HostBvh &h;
+    bool ok = true;
+    Box leaf_box(int32_t ref) const {
+        const uint32_t u = static_cast<uint32_t>(ref);
+        const uint32_t cnt = (u >> kBvhCountShift) & kBvhCountMask, first = u & ((1u << kBvhCountShift) - 1);
+        Box b;
+        for (uint32_t i = first; i < first + cnt; ++i) b.grow(slot[i]);
+        return b;
+    }
+    Box run4(int32_t ref) {
+        if (static_cast<uint32_t>(ref) & kBvhLeafBit) return leaf_box(ref);
+        Bvh4F &g = h.nodes4f[ref];
+        const int nc = h.nodes4[ref].n_children;
+        Box boxes[4], u;
+        int32_t refs[4];
+        for (int c = 0; c < nc; ++c) {
+            refs[c] = g.child[c];
+            boxes[c] = run4(refs[c]);
+            for (int k = 0; k < 3; ++k) { g.lo[k][c] = boxes[c].lo[k]; g.hi[k][c] = boxes[c].hi[k]; }
+            u.grow(boxes[c]);
+        }
+        Bvh4Node q;
+        ok = make_node4(boxes, refs, nc, q) && ok;
+        h.nodes4[ref] = q;
+        return u;
+    }
+    Box run2(int32_t ref) {
+        if (static_cast<uint32_t>(ref) & kBvhLeafBit) return leaf_box(ref);
+        BvhNode &n = h.nodes[ref];
+        Box u;
+        if (n.c0 != kBvhEmpty) {
+            const Box b = run2(n.c0);
+            for (int k = 0; k < 3; ++k) { n.lo0[k] = b.lo[k]; n.hi0[k] = b.hi[k]; }
+            u.grow(b);
+        }
+        if (n.c1 != kBvhEmpty) {
+            const Box b = run2(n.c1);
+            for (int k = 0; k < 3; ++k) { n.lo1[k] = b.lo[k]; n.hi1[k] = b.hi[k]; }
+            u.grow(b);
+        }
+        return u;
+    }
+};
+}  // namespace
+
+int refit_bvh(const HostScene &s, const std::vector<TriRec> &recs, HostBvh &h) {
+    const size_t nt = recs.size();
+    std::vector<uint8_t> cls;
+    built_classes(h, nt, cls);
+    std::vector<uint32_t> slot_of(nt, 0);
+    for (size_t i = 0; i < h.leaf_tris.size(); ++i) slot_of[h.leaf_tris[i]] = static_cast<uint32_t>(i);
+    std::vector<Box> slot(h.leaf_tris.size());
+    for (size_t t = 0; t < nt; ++t) {
+        Box b;
+        const int c = tri_class(recs[t], &s.verts[3 * s.tris[3 * t]], &s.verts[3 * s.tris[3 * t + 1]],
+                                &s.verts[3 * s.tris[3 * t + 2]], b.lo, b.hi);
+        if (c != cls[t]) return kRefitClassChange;
+        if (c == kTriTree) slot[slot_of[t]] = b;
+    }
+    HostBvh out = h;   // (a failed re-quantisation leaves h as it was)
+    out.scene_m1 = scene_m1_of(s.verts.data(), s.verts.size() / 3);
+    Refitter r{slot, out};
+    if (!out.leaf_tris.empty()) {
+        r.run4(0);
+        r.run2(0);
+    }
+    if (!r.ok) return kRefitClassChange;   // a box no 8-bit grid can bound: the rebuild reports it as creation does
+    h = std::move(out);
+    return RT_OK;
+}
+
+int requantize_bvh4(HostBvh &h) {
+    if (h.leaf_tris.empty()) return RT_OK;   // the empty tree's root has no child boxes
+    for (size_t i = 0; i < h.nodes4f.size(); ++i) {
+        const Bvh4F &g = h.nodes4f[i];
+        const int nc = h.nodes4[i].n_children;
+        Box boxes[4];
+        int32_t refs[4];
+        for (int c = 0; c < nc; ++c) {
+            refs[c] = g.child[c];
+            for (int k = 0; k < 3; ++k) { boxes[c].lo[k] = g.lo[k][c]; boxes[c].hi[k] = g.hi[k][c]; }
+        }
+        Bvh4Node q;
+        if (!make_node4(boxes, refs, nc, q)) return RT_E_ARG;
+        h.nodes4[i] = q;
+    }
+    return RT_OK;
+}
+
 namespace {
 // The float four-wide nodes (what the kernels read): the same topology as the quantised ones, and
 // every child box contains everything below it (its child boxes, its leaf triangles' padded

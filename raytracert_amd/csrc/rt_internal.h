@@ -136,6 +136,29 @@ struct HostBvh {
 bool acceptance_box(const TriRec &T, const float *v0, const float *v1, const float *v2, float lo[3], float hi[3],
                     bool *never);
 int build_bvh(const HostScene &s, const std::vector<TriRec> &recs, HostBvh &out);
+// acceptance_box's build-time knobs (bvh.cpp, where they are explained), here because the device refit
+// (rt_kernels.hip) restates it
+#ifndef RT_BVH_MAX_KE
+#define RT_BVH_MAX_KE 0.2
+#endif
+#ifndef RT_BVH_INPLANE_PAD
+#define RT_BVH_INPLANE_PAD 1
+#endif
+// Refit (rt_scene_update_vertices; argument in bvh.cpp): a triangle's class is baked into the topology.
+enum : int { kTriTree = 0, kTriAlways = 1, kTriNever = 2 };
+constexpr int kRefitClassChange = 1;   // refit_bvh: some triangle changed class (or a box cannot be quantised)
+// acceptance_box as a class; lo/hi are the padded box of a tree triangle
+int tri_class(const TriRec &T, const float *v0, const float *v1, const float *v2, float lo[3], float hi[3]);
+// the class each triangle was built with (leaf_tris: tree, always: always, the rest: never)
+void built_classes(const HostBvh &h, size_t nt, std::vector<uint8_t> &cls);
+// build_bvh's scene_m1 of nv vertices
+float scene_m1_of(const float *xyz, size_t nv);
+// Same topology, every box recomputed from s.verts / recs as the exact min/max union of what lies below
+// it, nodes4 re-quantised from the refitted child boxes, scene_m1 recomputed. RT_OK, or kRefitClassChange
+// with h untouched. What the device refit kernels compute, stated on the host.
+int refit_bvh(const HostScene &s, const std::vector<TriRec> &recs, HostBvh &h);
+// nodes4 re-quantised from nodes4f's child boxes (a tree read back from the device)
+int requantize_bvh4(HostBvh &h);
 float bvh4_decode(float origin, int ex, uint32_t q);
 uint64_t bvh_digest(const HostBvh &h);
 int validate_bvh(const HostScene &s, const std::vector<TriRec> &recs, const HostBvh &h, std::string &err);

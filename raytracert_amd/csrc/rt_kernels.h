@@ -208,6 +208,33 @@ void launch_face_normals(const float *xyz, const uint32_t *tri_v, int32_t nt, fl
 // uploads then pass every record through tri_rcp_slot (rt_internal.h).
 bool tri_rcp_records();
 void launch_normal_table(float4 *normals, float4 *ntab, int32_t nt, hipStream_t stream);
+// ---- dynamic geometry (rt_scene_update_vertices) ----
+// What a refit reports back in one small read: the class-change count and build_bvh's m1 (the bits of a
+// non-negative double, maximised as an integer). Zeroed before launch_refit_tris.
+struct RefitStatus {
+    unsigned long long m1_bits;
+    uint32_t class_changes;
+    uint32_t pad;
+};
+constexpr int32_t kRefitNeverSlot = INT32_MIN;   // tri_slot of a never-accepted triangle
+struct RefitArgs {
+    const float *xyz;          // 3 per vertex (nv)
+    const uint32_t *tri_v;     // 3 per triangle (nt)
+    int32_t nt, nv;
+    // the class each triangle was built with and where its record lives: >= 0 its leaf slot, -1 - k slot k
+    // of the always list, kRefitNeverSlot never accepted. Null: no tree (records and normals only).
+    const int32_t *tri_slot;
+    TriRec *tris, *leaf_recs, *always_recs;
+    float4 *normals, *ntab;
+    float4 *slot_box;          // per leaf slot: the padded acceptance box (lo, hi)
+    RefitStatus *status;
+};
+// One lane per triangle / vertex: records (tri_rcp_slot form when tri_rcp_records()), face normals, normal
+// table, acceptance boxes, classes, scene_m1 (k_refit_tris).
+void launch_refit_tris(const RefitArgs &a, hipStream_t stream);
+// One height of a tree: ids[0..n) are its nodes; call in increasing height, one launch each.
+void launch_refit_level4(Bvh4F *nodes, const int32_t *ids, int32_t n, const float4 *slot_box, hipStream_t stream);
+void launch_refit_level2(BvhNode *nodes, const int32_t *ids, int32_t n, const float4 *slot_box, hipStream_t stream);
 // Un-permute gathered tile shards ([nranks][slots][th][tw][3], tile g of the frames x T tiles in
 // rank g % nranks, slot g / nranks) into frames x height x width x 3 bytes; with slot0 / nslots, a
 // gather chunk holding slots [slot0, slot0 + nslots) of every rank ([nranks][nslots][th][tw][3]).

@@ -2675,6 +2675,202 @@ __global__ __launch_bounds__(kBlock) void k_normal_table(float4 *__restrict__ no
     normals[i] = make_float4(n0.x, n0.y, n0.z, ok ? 1.0f : 0.0f);
 }
 
+// ---- dynamic geometry: refit (rt_scene_update_vertices; argument in bvh.cpp) ----------------------
+// Everything below restates host code operation for operation (no contraction; f64 '/', sqrt and the
+// f64 -> f32 conversion are IEEE on gfx950), so a refitted device scene holds the bytes a fresh scene's
+// upload would: build_tri_records (scene_loader.cpp), k_face_normals + k_normal_table above, and
+// acceptance_box / down / up / build_bvh's scene_m1 (bvh.cpp). std::min / std::max are spelled out as the
+// compares they are.
+__device__ __forceinline__ double min_std(double a, double b) { return (b < a) ? b : a; }
+__device__ __forceinline__ double max_std(double a, double b) { return (a < b) ? b : a; }
+__device__ __forceinline__ float min_stdf(float a, float b) { return (b < a) ? b : a; }
+__device__ __forceinline__ bool finite_d(double v) { return fabs(v) < INFINITY; }   // false for NaN
+// bvh.cpp down / up: the float at or beyond v on the outside (nextafter towards -/+FLT_MAX by bit steps)
+__device__ __forceinline__ float round_down(double v) {
+    const float f = static_cast<float>(v);
+    if (!(static_cast<double>(f) > v) || f == -FLT_MAX) return f;
+    const int b = as_int(f);
+    if ((b & 0x7fffffff) == 0) return as_float(static_cast<int>(0x80000001u));
+    return as_float(f > 0.0f ? b - 1 : b + 1);
+}
+__device__ __forceinline__ float round_up(double v) {
+    const float f = static_cast<float>(v);
+    if (!(static_cast<double>(f) < v) || f == FLT_MAX) return f;
+    const int b = as_int(f);
+    if ((b & 0x7fffffff) == 0) return as_float(0x00000001);
+    return as_float(f > 0.0f ? b + 1 : b - 1);
+}
+
+// acceptance_box (bvh.cpp) as a class (kTriTree / kTriAlways / kTriNever); lo / hi for a tree triangle.
+__device__ int refit_class(const float n[3], float uu_f, float vv_f, float D_f, const V3 &p0, const V3 &p1, const V3 &p2,
+                           float lo[3], float hi[3]) {
+    if (n[0] == 0 && n[1] == 0 && n[2] == 0) return kTriNever;
+    const double uu = uu_f, vv = vv_f, D = D_f;
+    if (!finite_d(D) || D == 0.0 || !finite_d(uu) || !finite_d(vv) || !(uu > 0) || !(vv > 0)) return kTriAlways;
+    const double c = fabs(D) / (uu * vv);
+    const double L = sqrt(max_std(uu, vv));
+    if (!finite_d(c) || !finite_d(L) || c <= 0) return kTriAlways;
+    const double K = 36.0 / c + 18.0 / (c * sqrt(c)) + 2.0 / sqrt(c);
+    const double ke = K * 5.9604644775390625e-08;
+    if (!(ke <= RT_BVH_MAX_KE)) return kTriAlways;
+    const double pad = 4.0 * 2.0 * ke * L / (1.0 - ke);
+    const double a0[3] = {double(p0.x), double(p0.y), double(p0.z)};
+    const double a1[3] = {double(p1.x), double(p1.y), double(p1.z)};
+    const double a2[3] = {double(p2.x), double(p2.y), double(p2.z)};
+    double e1[3], e2[3], nd[3];
+    for (int k = 0; k < 3; ++k) { e1[k] = a1[k] - a0[k]; e2[k] = a2[k] - a0[k]; }
+    nd[0] = e1[1] * e2[2] - e1[2] * e2[1];
+    nd[1] = e1[2] * e2[0] - e1[0] * e2[2];
+    nd[2] = e1[0] * e2[1] - e1[1] * e2[0];
+    const double n2 = nd[0] * nd[0] + nd[1] * nd[1] + nd[2] * nd[2];
+    for (int k = 0; k < 3; ++k) {
+        const double along = !RT_BVH_INPLANE_PAD ? 1.0 : n2 > 0 ? min_std(1.0, sqrt(max_std(0.0, 1.0 - nd[k] * nd[k] / n2) + 1e-12)) : 1.0;
+        const double pk = pad * along + 1e-7 * L;
+        double mn = a0[k], mx = a0[k];
+        if (a1[k] < mn) mn = a1[k];
+        if (a2[k] < mn) mn = a2[k];
+        if (mx < a1[k]) mx = a1[k];
+        if (mx < a2[k]) mx = a2[k];
+        lo[k] = round_down(mn - pk);
+        hi[k] = round_up(mx + pk);
+    }
+    return kTriTree;
+}
+
+// One lane per triangle (and per vertex, for scene_m1): the triangle's record into d_tris and into its
+// leaf or always slot, its face normal and normal table, its padded acceptance box into its leaf slot's
+// box, and its class against the class it was built with (a.tri_slot; null: no tree, records and normals
+// only). Nothing here is read by the same launch: the traversal kernels fetch the records in later ones.
+__global__ __launch_bounds__(kBlock) void k_refit_tris(const RefitArgs a) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    // build_bvh's m1: max over vertices of |x| + |y| + |z| in double. Non-negative doubles order as their
+    // bit patterns; a NaN sum never wins std::max on the host, so it contributes 0 here.
+    unsigned long long m = 0;
+    if (i < a.nv) {
+        const double v = fabs(double(a.xyz[3 * i])) + fabs(double(a.xyz[3 * i + 1])) + fabs(double(a.xyz[3 * i + 2]));
+        if (v == v) m = static_cast<unsigned long long>(__double_as_longlong(v));
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long x = __shfl_xor(m, o);
+        m = x > m ? x : m;
+    }
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(&a.status->m1_bits, m);
+    if (i >= a.nt) return;
+    const uint32_t ia = a.tri_v[3 * i], ib = a.tri_v[3 * i + 1], ic = a.tri_v[3 * i + 2];
+    const V3 p0 = mk(a.xyz[3 * ia], a.xyz[3 * ia + 1], a.xyz[3 * ia + 2]);
+    const V3 p1 = mk(a.xyz[3 * ib], a.xyz[3 * ib + 1], a.xyz[3 * ib + 2]);
+    const V3 p2 = mk(a.xyz[3 * ic], a.xyz[3 * ic + 1], a.xyz[3 * ic + 2]);
+    const V3 u = sub(p1, p0), v = sub(p2, p0);                                     // raytracing.cpp:106-107
+    const V3 n = mk(u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x);   // :108
+    const float uu = dot(u, u), uv = dot(u, v), vv = dot(v, v);                    // :134-136
+    const float D = uv * uv - uu * vv;                                             // :140
+    float dslot = D;
+    if (RT_TRI_RCP) {   // tri_rcp_slot (rt_internal.h)
+        const float ad = fabsf(D);
+        const int ex = (as_int(D) >> 23) & 0xff;
+        dslot = (ex != 0 && ex != 0xff && ad >= 0x1p-30f && ad <= 0x1p30f) ? 1.0f / D : as_float(0x7fc00000);
+    }
+    const float4 q0 = make_float4(p0.x, p0.y, p0.z, uu), q1 = make_float4(u.x, u.y, u.z, uv);
+    const float4 q2 = make_float4(v.x, v.y, v.z, vv), q3 = make_float4(n.x, n.y, n.z, dslot);
+    float4 *t = reinterpret_cast<float4 *>(a.tris + i);
+    t[0] = q0; t[1] = q1; t[2] = q2; t[3] = q3;
+    // k_face_normals and k_normal_table
+    V3 n0 = n;
+    normalize(n0);
+    V3 n1 = n0;
+    normalize(n1);
+    V3 n2 = n1;
+    normalize(n2);
+    V3 n3 = n2;
+    normalize(n3);
+    const bool ok = as_int(n3.x) == as_int(n1.x) && as_int(n3.y) == as_int(n1.y) && as_int(n3.z) == as_int(n1.z);
+    a.ntab[2 * i] = make_float4(n1.x, n1.y, n1.z, 0.0f);
+    a.ntab[2 * i + 1] = make_float4(n2.x, n2.y, n2.z, 0.0f);
+    a.normals[i] = make_float4(n0.x, n0.y, n0.z, ok ? 1.0f : 0.0f);
+    if (!a.tri_slot) return;
+    const float nn[3] = {n.x, n.y, n.z};
+    float lo[3], hi[3];
+    const int cls = refit_class(nn, uu, vv, D, p0, p1, p2, lo, hi);
+    const int32_t slot = a.tri_slot[i];
+    const int built = slot >= 0 ? kTriTree : slot == kRefitNeverSlot ? kTriNever : kTriAlways;
+    if (cls != built) { atomicAdd(&a.status->class_changes, 1u); return; }
+    if (cls == kTriTree) {
+        float4 *r = reinterpret_cast<float4 *>(a.leaf_recs + slot);
+        r[0] = q0; r[1] = q1; r[2] = q2; r[3] = q3;
+        a.slot_box[2 * static_cast<int64_t>(slot)] = make_float4(lo[0], lo[1], lo[2], 0.0f);
+        a.slot_box[2 * static_cast<int64_t>(slot) + 1] = make_float4(hi[0], hi[1], hi[2], 0.0f);
+    } else if (cls == kTriAlways) {
+        float4 *r = reinterpret_cast<float4 *>(a.always_recs + (-1 - slot));
+        r[0] = q0; r[1] = q1; r[2] = q2; r[3] = q3;
+    }
+}
+
+// Box of everything below a child ref whose own boxes are final: a leaf's slots in order, or an inner
+// node's child boxes in order (bvh.cpp Box::grow: min / max as compares, from an inverted FLT_MAX box).
+struct RBox { float lo[3], hi[3]; };
+__device__ __forceinline__ void rgrow(RBox &b, const float lo[3], const float hi[3]) {
+    for (int k = 0; k < 3; ++k) { b.lo[k] = min_stdf(b.lo[k], lo[k]); b.hi[k] = max_std(b.hi[k], hi[k]); }
+}
+__device__ __forceinline__ RBox leaf_union(int32_t ref, const float4 *__restrict__ slot_box) {
+    RBox b{{FLT_MAX, FLT_MAX, FLT_MAX}, {-FLT_MAX, -FLT_MAX, -FLT_MAX}};
+    const uint32_t u = static_cast<uint32_t>(ref);
+    const uint32_t cnt = (u >> kBvhCountShift) & kBvhCountMask, first = u & ((1u << kBvhCountShift) - 1);
+    for (uint32_t s = first; s < first + cnt; ++s) {
+        const float4 l = slot_box[2 * static_cast<int64_t>(s)], h = slot_box[2 * static_cast<int64_t>(s) + 1];
+        const float lo[3] = {l.x, l.y, l.z}, hi[3] = {h.x, h.y, h.z};
+        rgrow(b, lo, hi);
+    }
+    return b;
+}
+
+// One height of the four-wide tree per launch (ids: the nodes of this height; every inner child is of a
+// lower height, finished by an earlier launch: the kernel boundary carries the data, also across XCDs).
+// One lane per (node, child). Writes box fields only; empty slots stay inverted.
+__global__ __launch_bounds__(kBlock) void k_refit_level4(Bvh4F *__restrict__ nodes, const int32_t *__restrict__ ids, int32_t n,
+                                                         const float4 *__restrict__ slot_box) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (i >= 4 * static_cast<int64_t>(n)) return;
+    const int32_t id = ids[i >> 2];
+    const int c = static_cast<int>(i & 3);
+    const int32_t ref = nodes[id].child[c];
+    if (ref == kBvhEmpty) return;
+    RBox b;
+    if (static_cast<uint32_t>(ref) & kBvhLeafBit) {
+        b = leaf_union(ref, slot_box);
+    } else {
+        b = RBox{{FLT_MAX, FLT_MAX, FLT_MAX}, {-FLT_MAX, -FLT_MAX, -FLT_MAX}};
+        const Bvh4F &g = nodes[ref];
+        for (int j = 0; j < 4; ++j) {
+            if (g.child[j] == kBvhEmpty) continue;
+            const float lo[3] = {g.lo[0][j], g.lo[1][j], g.lo[2][j]}, hi[3] = {g.hi[0][j], g.hi[1][j], g.hi[2][j]};
+            rgrow(b, lo, hi);
+        }
+    }
+    for (int k = 0; k < 3; ++k) { nodes[id].lo[k][c] = b.lo[k]; nodes[id].hi[k][c] = b.hi[k]; }
+}
+
+// The same for the binary tree: one lane per (node, side).
+__global__ __launch_bounds__(kBlock) void k_refit_level2(BvhNode *__restrict__ nodes, const int32_t *__restrict__ ids, int32_t n,
+                                                         const float4 *__restrict__ slot_box) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (i >= 2 * static_cast<int64_t>(n)) return;
+    const int32_t id = ids[i >> 1];
+    const int side = static_cast<int>(i & 1);
+    const int32_t ref = side ? nodes[id].c1 : nodes[id].c0;
+    if (ref == kBvhEmpty) return;
+    RBox b;
+    if (static_cast<uint32_t>(ref) & kBvhLeafBit) {
+        b = leaf_union(ref, slot_box);
+    } else {
+        b = RBox{{FLT_MAX, FLT_MAX, FLT_MAX}, {-FLT_MAX, -FLT_MAX, -FLT_MAX}};
+        const BvhNode &g = nodes[ref];
+        if (g.c0 != kBvhEmpty) rgrow(b, g.lo0, g.hi0);
+        if (g.c1 != kBvhEmpty) rgrow(b, g.lo1, g.hi1);
+    }
+    float *lo = side ? nodes[id].lo1 : nodes[id].lo0, *hi = side ? nodes[id].hi1 : nodes[id].hi0;
+    for (int k = 0; k < 3; ++k) { lo[k] = b.lo[k]; hi[k] = b.hi[k]; }
+}
+
 // rayIntersectTriangle (raytracing.cpp:99-154) for n independent (ray, triangle) pairs, every
 // step in the reference's order; unlike intersectMesh's use of it there is no distance compare, so
 // a hit whose point is NaN or infinite is still reported, as the reference returns true for it.
@@ -3186,6 +3382,22 @@ void launch_normal_table(float4 *normals, float4 *ntab, int32_t nt, hipStream_t 
 void launch_face_normals(const float *xyz, const uint32_t *tri_v, int32_t nt, float4 *normals, hipStream_t stream) {
     if (nt <= 0) return;
     hipLaunchKernelGGL(k_face_normals, dim3(grid_for(nt)), dim3(kBlock), 0, stream, xyz, tri_v, nt, normals);
+}
+
+void launch_refit_tris(const RefitArgs &a, hipStream_t stream) {
+    const int64_t n = std::max<int64_t>(a.nt, a.nv);
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_refit_tris, dim3(grid_for(n)), dim3(kBlock), 0, stream, a);
+}
+
+void launch_refit_level4(Bvh4F *nodes, const int32_t *ids, int32_t n, const float4 *slot_box, hipStream_t stream) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_refit_level4, dim3(grid_for(4 * static_cast<int64_t>(n))), dim3(kBlock), 0, stream, nodes, ids, n, slot_box);
+}
+
+void launch_refit_level2(BvhNode *nodes, const int32_t *ids, int32_t n, const float4 *slot_box, hipStream_t stream) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_refit_level2, dim3(grid_for(2 * static_cast<int64_t>(n))), dim3(kBlock), 0, stream, nodes, ids, n, slot_box);
 }
 
 void launch_ray_triangle_pairs(const float *R, const float *T, int32_t n, uint8_t *hit, float *I, hipStream_t stream) {

@@ -13,6 +13,7 @@
 #   e2e          bench.py --e2e-only: render -> host -> PPM per C4 frame
 #   ab           same-box A/B of library builds (AB_LIBS: names of raytracert_amd/ab/lib_<name>.so, 'cur' = the
 #                in-tree build; AB_PASSES; AB_WORKLOADS; AB_ARGS extra bench arguments): the timed loop only
+#   refit        tools/refit_probe.py: update / re-create / frame times of C4 and C5 under a deformation
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"
 TAG=$1; shift
@@ -70,6 +71,9 @@ for STEP in "$@"; do
           done
         done
       done ;;
+    refit)
+      timeout -k 10 500 python -u tools/refit_probe.py profiles/refit_probe.json > $TMPDIR/refit_probe_$TAG.log 2>&1 || fail refit $TMPDIR/refit_probe_$TAG.log
+      cat profiles/refit_probe.json ;;
     *) echo "unknown step $STEP"; exit 2 ;;
   esac
 done
