@@ -181,6 +181,30 @@ int  rt_scene_update_vertices(rt_scene *scene, const float *xyz, int32_t n_verti
 int  rt_scene_update_vertices_device(rt_scene *scene, const void *d_xyz, int32_t n_vertices, int32_t mode,
                                      int32_t *outcome);
 
+/* ---- tree builder ---------------------------------------------------------------------
+ * Which builder makes a scene's trees. Every builder gives the same output bytes (any tree whose boxes
+ * contain the padded acceptance boxes below them does); they differ in build time and frame time.
+ * RT_BUILD_SAH, the default, is the host's binned-SAH build. RT_BUILD_LBVH is a Morton-order radix tree
+ * (Karras 2012): on a device scene it is built by HIP kernels from the device-resident vertices, with
+ * no host build and no upload; on a host-only scene the same tree is built on the CPU. A tree that
+ * would break a limit of the traversal (more than 40 levels, the leaf index field, boxes that cannot
+ * be quantised) is built by the SAH builder instead, without an error.
+ * rt_scene_set_builder rebuilds nothing: it chooses the builder of the scene's later builds
+ * (RT_UPDATE_REBUILD, RT_UPDATE_AUTO's rebuild after a class change, a lazy first build). RT_E_ARG
+ * (scene untouched) for an unknown value. rt_scene_get_builder reports the chosen builder and the one
+ * that built the trees the scene holds now (either pointer may be NULL).
+ * *outcome of rt_scene_update_vertices[_device] is RT_UPDATED_REBUILT_LBVH when the Morton-order
+ * builder made the new trees; RT_UPDATED_REBUILT keeps meaning the host SAH build.
+ * rt_scene_create_ex is rt_scene_create with the builder of the scene's first trees. */
+#define RT_BUILD_SAH   0
+#define RT_BUILD_LBVH  1
+#define RT_UPDATED_REBUILT_LBVH 2
+int  rt_scene_set_builder(rt_scene *scene, int32_t builder);
+int  rt_scene_get_builder(const rt_scene *scene, int32_t *selected, int32_t *built_with);
+int  rt_scene_create_ex(const float *xyz, int32_t n_vertices, const uint32_t *tri_v, const uint32_t *tri_mat,
+                        int32_t n_triangles, const rt_material *materials, int32_t n_materials,
+                        int32_t device, int32_t builder, rt_scene **out);
+
 /* ---- hot path ------------------------------------------------------------------------- */
 /* rayIntersectTriangle (raytracing.cpp:99-154) for n independent (ray, triangle) pairs on device
  * `device`: rays = n x {origin, dest} (6 floats), tris = n x {T0, T1, T2} (9 floats), host arrays.

@@ -63,6 +63,9 @@ LOAD_TEXCOORDS = 0x10
 WORK_FIELDS = 6
 UPDATE_AUTO, UPDATE_REBUILD = 0, 1      # rt_scene_update_vertices modes
 UPDATED_REFIT, UPDATED_REBUILT = 0, 1   # ... and outcomes
+UPDATED_REBUILT_LBVH = 2                # ... the trees rebuilt by the Morton-order builder
+BUILD_SAH, BUILD_LBVH = 0, 1            # rt_scene_set_builder
+BUILDERS = ("sah", "lbvh")
 
 
 class RtParams(C.Structure):
@@ -109,6 +112,9 @@ _SIGNATURES = {
     "rt_scene_destroy": ([_VP], None),
     "rt_scene_info": ([_VP, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)], C.c_int),
     "rt_scene_export": ([_VP, _VP, _VP, _VP, _VP, _VP], C.c_int),
+    "rt_scene_create_ex": ([_VP, C.c_int32, _VP, _VP, C.c_int32, _VP, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_VP)], C.c_int),
+    "rt_scene_set_builder": ([_VP, C.c_int32], C.c_int),
+    "rt_scene_get_builder": ([_VP, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], C.c_int),
     "rt_scene_update_vertices": ([_VP, _VP, C.c_int32, C.c_int32, C.POINTER(C.c_int32)], C.c_int),
     "rt_scene_update_vertices_device": ([_VP, _VP, C.c_int32, C.c_int32, C.POINTER(C.c_int32)], C.c_int),
     "rt_get_material": ([_VP, C.c_int32, C.POINTER(RtMaterial)], C.c_int),

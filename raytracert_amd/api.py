@@ -116,6 +116,14 @@ class RenderParams:
         return p
 
 
+def _builder_id(name) -> int:
+    if isinstance(name, str):
+        if name not in _capi.BUILDERS:
+            raise ValueError(f"unknown builder {name!r} (one of {_capi.BUILDERS})")
+        return _capi.BUILDERS.index(name)
+    return int(name)
+
+
 class Scene:
     """A loaded mesh bound to one GPU (or host-only with device=-1)."""
 
@@ -138,7 +146,10 @@ class Scene:
         return cls(h, device)
 
     @classmethod
-    def create(cls, vertices, triangles, tri_mat, materials: Sequence[dict], device: int = 0) -> "Scene":
+    def create(cls, vertices, triangles, tri_mat, materials: Sequence[dict], device: int = 0,
+               builder: str = "sah") -> "Scene":
+        """rt_scene_create_ex. builder 'sah' (the host's binned-SAH build, the default) or 'lbvh' (a
+        Morton-order radix tree; on a device scene built by HIP kernels with no host build)."""
         v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
         t = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
         m = np.ascontiguousarray(tri_mat, np.uint32).reshape(-1)
@@ -151,9 +162,20 @@ class Scene:
             mats[i].Ns, mats[i].Ni, mats[i].Tr = d.get("Ns", 0.0), d.get("Ni", 0.0), d.get("Tr", 0.0)
             mats[i].illum, mats[i].flags = d.get("illum", 0), d.get("flags", 0)
         h = C.c_void_p()
-        check(lib().rt_scene_create(_ptr(v), len(v), _ptr(t), _ptr(m), len(m), C.cast(mats, C.c_void_p),
-                                    len(materials), device, C.byref(h)))
+        check(lib().rt_scene_create_ex(_ptr(v), len(v), _ptr(t), _ptr(m), len(m), C.cast(mats, C.c_void_p),
+                                       len(materials), device, _builder_id(builder), C.byref(h)))
         return cls(h, device)
+
+    def set_builder(self, name: str) -> None:
+        """rt_scene_set_builder: the builder of the scene's later builds ('sah' or 'lbvh'); rebuilds nothing."""
+        check(lib().rt_scene_set_builder(self._h, _builder_id(name)))
+
+    @property
+    def builder(self) -> tuple[str, str]:
+        """(selected, built_with): the chosen builder and the one that built the trees the scene holds."""
+        sel, built = C.c_int32(), C.c_int32()
+        check(lib().rt_scene_get_builder(self._h, C.byref(sel), C.byref(built)))
+        return _capi.BUILDERS[sel.value], _capi.BUILDERS[built.value]
 
     def close(self) -> None:
         if self._h:
@@ -198,7 +220,8 @@ class Scene:
         """rt_scene_update_vertices: new positions for the scene's vertices (dynamic geometry). `vertices`
         is a float32 (n, 3) array, or a CUDA torch tensor of that shape on the scene's device, which goes
         through rt_scene_update_vertices_device with no host copy. mode 'auto' refits the BVH and rebuilds
-        it only if some triangle changed class; 'rebuild' always rebuilds. Returns 'refit' or 'rebuilt';
+        it only if some triangle changed class; 'rebuild' always rebuilds. Returns 'refit', 'rebuilt' (the
+        host SAH build) or 'rebuilt_lbvh' (the Morton-order builder, see set_builder);
         either way the scene then behaves bit for bit as one created from the new vertices."""
         m = {"auto": _capi.UPDATE_AUTO, "rebuild": _capi.UPDATE_REBUILD}.get(mode, mode)
         out = C.c_int32(-1)
@@ -214,7 +237,7 @@ class Scene:
             if v.ndim != 2 or v.shape[1] != 3:
                 raise ValueError("update_vertices: a float32 (n, 3) array is required")
             check(lib().rt_scene_update_vertices(self._h, _ptr(v), len(v), int(m), C.byref(out)))
-        return "refit" if out.value == _capi.UPDATED_REFIT else "rebuilt"
+        return {_capi.UPDATED_REFIT: "refit", _capi.UPDATED_REBUILT_LBVH: "rebuilt_lbvh"}.get(out.value, "rebuilt")
 
     def texcoords(self) -> tuple[np.ndarray, np.ndarray]:
         """rt_scene_texcoords (a scene loaded with texcoords=True): (texcoords[n, 3] float32 with z = 0,

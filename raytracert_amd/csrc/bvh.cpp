@@ -44,6 +44,7 @@
 #include <vector>
 
 #include "rt_internal.h"
+#include "lbvh_shared.h"
 
 namespace rt {
 namespace {
@@ -683,6 +684,155 @@ int requantize_bvh4(HostBvh &h) {
         h.nodes4[i] = q;
     }
     return RT_OK;
+}
+
+int nodes4_from_nodes4f(HostBvh &h) {
+    h.nodes4.assign(h.nodes4f.size(), Bvh4Node{});
+    for (size_t i = 0; i < h.nodes4f.size(); ++i) {
+        int nc = 0;
+        while (nc < 4 && h.nodes4f[i].child[nc] != kBvhEmpty) ++nc;
+        h.nodes4[i].n_children = static_cast<uint8_t>(nc);
+    }
+    if (h.leaf_tris.empty()) return make_node4(nullptr, nullptr, 0, h.nodes4[0]) ? RT_OK : RT_E_ARG;
+    return requantize_bvh4(h);
+}
+
+// ---- the Morton-order builder (RT_BUILD_LBVH; DESIGN.md "GPU BVH build") --------------------------
+// The host statement of what the k_lbvh_* kernels build, array for array: the same classes and boxes,
+// the same keys, sort, radix tree (lbvh_shared.h), numbering, boxes and four-wide collapse. By the
+// exactness argument at the top of this file the builder cannot change an output byte, only speed.
+int lbvh_depth_limit() {
+    int limit = kMaxBvhDepth;
+    if (const char *e = std::getenv("RTAMD_LBVH_MAX_DEPTH")) limit = std::atoi(e);   // tests
+    return std::min(std::max(limit, 1), kMaxBvhDepth);
+}
+
+int build_lbvh(const HostScene &s, const std::vector<TriRec> &recs, HostBvh &out) {
+    out = HostBvh();
+    const size_t nt = recs.size();
+    out.scene_m1 = scene_m1_of(s.verts.data(), s.verts.size() / 3);
+    // classes and boxes; tree triangles in triangle order
+    std::vector<Box> box;
+    std::vector<uint32_t> tree;
+    for (size_t i = 0; i < nt; ++i) {
+        Box b;
+        const int c = tri_class(recs[i], &s.verts[3 * s.tris[3 * i]], &s.verts[3 * s.tris[3 * i + 1]],
+                                &s.verts[3 * s.tris[3 * i + 2]], b.lo, b.hi);
+        if (c == kTriTree) { tree.push_back(static_cast<uint32_t>(i)); box.push_back(b); }
+        else if (c == kTriAlways) out.always.push_back(static_cast<uint32_t>(i));
+        else out.n_never++;
+    }
+    const int32_t np = static_cast<int32_t>(tree.size());
+    if (tree.size() >= (size_t(1) << kBvhCountShift)) return kLbvhFallback;   // leaf first-index field
+    const int limit = lbvh_depth_limit();
+    auto bits = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
+    auto unbits = [](uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; };
+    // keys: centroid of the padded box, 10 bits per axis over the centroid bounds
+    std::vector<float> cen(3 * size_t(np));
+    uint32_t kmin[3] = {~0u, ~0u, ~0u}, kmax[3] = {0, 0, 0};
+    for (int32_t j = 0; j < np; ++j)
+        for (int k = 0; k < 3; ++k) {
+            const float c = 0.5f * (box[j].lo[k] + box[j].hi[k]);
+            cen[3 * size_t(j) + k] = c;
+            const uint32_t key = lbvh_ordered(bits(c));
+            kmin[k] = std::min(kmin[k], key);
+            kmax[k] = std::max(kmax[k], key);
+        }
+    std::vector<uint32_t> code0(np);
+    for (int32_t j = 0; j < np; ++j) {
+        uint32_t q[3];
+        for (int k = 0; k < 3; ++k) q[k] = lbvh_cell(cen[3 * size_t(j) + k], unbits(lbvh_unordered(kmin[k])), unbits(lbvh_unordered(kmax[k])));
+        code0[j] = lbvh_code(q[0], q[1], q[2]);
+    }
+    // stable sort by code (the kernels: four stable 8-bit radix passes)
+    std::vector<int32_t> perm(np);
+    std::iota(perm.begin(), perm.end(), 0);
+    std::stable_sort(perm.begin(), perm.end(), [&](int32_t a, int32_t b) { return code0[a] < code0[b]; });
+    std::vector<uint32_t> codes(np);
+    std::vector<Box> slot(np);
+    out.leaf_tris.resize(np);
+    for (int32_t j = 0; j < np; ++j) { codes[j] = code0[perm[j]]; slot[j] = box[perm[j]]; out.leaf_tris[j] = tree[perm[j]]; }
+    auto ref_leaf = [](int32_t first, int32_t count) {
+        return static_cast<int32_t>(kBvhLeafBit | (static_cast<uint32_t>(count) << kBvhCountShift) | static_cast<uint32_t>(first));
+    };
+    if (np <= kMaxLeaf) {   // empty tree, or the whole tree is one leaf wrapped in a root (as build_bvh)
+        BvhNode root{};
+        for (int k = 0; k < 3; ++k) { root.lo0[k] = root.lo1[k] = FLT_MAX; root.hi0[k] = root.hi1[k] = -FLT_MAX; }
+        root.c0 = root.c1 = kBvhEmpty;
+        Bvh4F g = make_node4f(nullptr, nullptr, 0);
+        out.depth = 1;
+        if (np > 0) {
+            Box b;
+            for (int32_t j = 0; j < np; ++j) b.grow(slot[j]);
+            root.c0 = ref_leaf(0, np);
+            for (int k = 0; k < 3; ++k) { root.lo0[k] = b.lo[k]; root.hi0[k] = b.hi[k]; }
+            g = make_node4f(&b, &root.c0, 1);
+            out.depth = 2;
+        }
+        if (out.depth > limit) return kLbvhFallback;
+        out.nodes.push_back(root);
+        out.nodes4f.push_back(g);
+        out.depth4 = 1;
+        return nodes4_from_nodes4f(out) == RT_OK ? RT_OK : kLbvhFallback;
+    }
+    // topology: one radix-tree node per i in [0, np - 1); nodes over more than kMaxLeaf codes are emitted
+    const int32_t ni = np - 1;
+    std::vector<LbvhRange> rg(ni);
+    std::vector<int32_t> parent(ni, -1);
+    for (int32_t i = 0; i < ni; ++i) {
+        rg[i] = lbvh_node(codes.data(), np, i);
+        if (rg[i].split != rg[i].first) parent[rg[i].split] = i;
+        if (rg[i].split + 1 != rg[i].last) parent[rg[i].split + 1] = i;
+    }
+    auto emitted = [&](int32_t i) { return rg[i].last - rg[i].first + 1 > kMaxLeaf; };
+    std::vector<int32_t> depth(ni, 0), id2(ni, -1), id4(ni, -1);
+    int32_t n2 = 0, n4 = 0, max_depth = 0, max_even = 0;
+    for (int32_t i = 0; i < ni; ++i) {
+        int32_t d = 0;
+        for (int32_t p = parent[i]; p >= 0 && d <= kMaxBvhDepth; p = parent[p]) ++d;
+        depth[i] = d;
+        if (!emitted(i)) continue;
+        id2[i] = n2++;
+        max_depth = std::max(max_depth, d);
+        if ((d & 1) == 0) { id4[i] = n4++; max_even = std::max(max_even, d); }
+    }
+    out.depth = max_depth + 2;   // the deepest emitted node's children are leaves
+    out.depth4 = max_even / 2 + 1;
+    if (out.depth > limit) return kLbvhFallback;
+    auto child_ref = [&](int32_t a, int32_t b, int32_t inner) { return b - a + 1 > kMaxLeaf ? id2[inner] : ref_leaf(a, b - a + 1); };
+    out.nodes.assign(n2, BvhNode{});
+    for (int32_t i = 0; i < ni; ++i) {
+        if (id2[i] < 0) continue;
+        BvhNode &g = out.nodes[id2[i]];
+        g.c0 = child_ref(rg[i].first, rg[i].split, rg[i].split);
+        g.c1 = child_ref(rg[i].split + 1, rg[i].last, rg[i].split + 1);
+    }
+    // boxes bottom-up: each child box the exact union of what lies below it (the refit's statement)
+    Refitter{slot, out}.run2(0);
+    // four-wide: the emitted nodes at even depth; children are the grandchildren, or a child that is a leaf
+    std::vector<int32_t> four_of(n2, -1);
+    for (int32_t i = 0; i < ni; ++i)
+        if (id4[i] >= 0) four_of[id2[i]] = id4[i];
+    out.nodes4f.assign(n4, make_node4f(nullptr, nullptr, 0));
+    for (int32_t a = 0; a < n2; ++a) {
+        if (four_of[a] < 0) continue;
+        Bvh4F &g = out.nodes4f[four_of[a]];
+        int nc = 0;
+        auto put = [&](int32_t ref, const float *lo, const float *hi) {
+            g.child[nc] = (static_cast<uint32_t>(ref) & kBvhLeafBit) ? ref : four_of[ref];
+            for (int k = 0; k < 3; ++k) { g.lo[k][nc] = lo[k]; g.hi[k][nc] = hi[k]; }
+            ++nc;
+        };
+        const BvhNode &n = out.nodes[a];
+        for (int side = 0; side < 2; ++side) {
+            const int32_t ref = side ? n.c1 : n.c0;
+            if (static_cast<uint32_t>(ref) & kBvhLeafBit) { put(ref, side ? n.lo1 : n.lo0, side ? n.hi1 : n.hi0); continue; }
+            const BvhNode &m = out.nodes[ref];
+            put(m.c0, m.lo0, m.hi0);
+            put(m.c1, m.lo1, m.hi1);
+        }
+    }
+    return nodes4_from_nodes4f(out) == RT_OK ? RT_OK : kLbvhFallback;
 }
 
 namespace {

@@ -144,6 +144,9 @@ int build_bvh(const HostScene &s, const std::vector<TriRec> &recs, HostBvh &out)
 #ifndef RT_BVH_INPLANE_PAD
 #define RT_BVH_INPLANE_PAD 1
 #endif
+#ifndef RT_BVH_MAX_LEAF
+#define RT_BVH_MAX_LEAF 2   // triangles per leaf (bvh.cpp; the device builder restates it)
+#endif
 // Refit (rt_scene_update_vertices; argument in bvh.cpp): a triangle's class is baked into the topology.
 enum : int { kTriTree = 0, kTriAlways = 1, kTriNever = 2 };
 constexpr int kRefitClassChange = 1;   // refit_bvh: some triangle changed class (or a box cannot be quantised)
@@ -159,6 +162,14 @@ float scene_m1_of(const float *xyz, size_t nv);
 int refit_bvh(const HostScene &s, const std::vector<TriRec> &recs, HostBvh &h);
 // nodes4 re-quantised from nodes4f's child boxes (a tree read back from the device)
 int requantize_bvh4(HostBvh &h);
+// nodes4 made from nodes4f alone (a tree built on the device: child counts, then requantize_bvh4)
+int nodes4_from_nodes4f(HostBvh &h);
+// The Morton-order radix tree (RT_BUILD_LBVH), the host statement of the k_lbvh_* kernels: RT_OK, or
+// kLbvhFallback when the tree would break a limit (deeper than lbvh_depth_limit(), leaf index field,
+// boxes that cannot be quantised); the caller then builds with build_bvh.
+constexpr int kLbvhFallback = 2;
+int lbvh_depth_limit();   // kMaxBvhDepth, lowered by RTAMD_LBVH_MAX_DEPTH (tests), read at each build
+int build_lbvh(const HostScene &s, const std::vector<TriRec> &recs, HostBvh &out);
 float bvh4_decode(float origin, int ex, uint32_t q);
 uint64_t bvh_digest(const HostBvh &h);
 int validate_bvh(const HostScene &s, const std::vector<TriRec> &recs, const HostBvh &h, std::string &err);

@@ -235,6 +235,50 @@ void launch_refit_tris(const RefitArgs &a, hipStream_t stream);
 // One height of a tree: ids[0..n) are its nodes; call in increasing height, one launch each.
 void launch_refit_level4(Bvh4F *nodes, const int32_t *ids, int32_t n, const float4 *slot_box, hipStream_t stream);
 void launch_refit_level2(BvhNode *nodes, const int32_t *ids, int32_t n, const float4 *slot_box, hipStream_t stream);
+// ---- GPU BVH build (RT_BUILD_LBVH; DESIGN.md "GPU BVH build", host statement: bvh.cpp build_lbvh) ----
+constexpr int kLbvhSortItems = 2048;              // keys per workgroup of the radix passes
+constexpr int kLbvhHeights = kMaxBvhDepth + 1;
+// The one record a build reports back (zeroed before the build).
+struct LbvhStatus {
+    unsigned long long m1_bits;                   // as RefitStatus::m1_bits
+    uint32_t cen_min[3], cen_max[3];              // centroid bounds as lbvh_ordered keys
+    uint32_t np, np_na, nt_split;                 // tree triangles; tree + always; all (the class split's offsets)
+    uint32_t n2, n4;                              // nodes of the binary / four-wide tree
+    uint32_t max_depth, max_even;                 // deepest emitted node; deepest at even depth
+    uint32_t root_done;                           // the sweeps reached the root
+    uint32_t error;                               // internal inconsistency (never set by a correct build)
+    uint32_t cnt2[kLbvhHeights], cnt4[kLbvhHeights];   // nodes per height (four-wide: per height group)
+    uint32_t off2[kLbvhHeights + 1], off4[kLbvhHeights + 1];
+    uint32_t cur2[kLbvhHeights], cur4[kLbvhHeights];
+};
+struct LbvhArgs {
+    const float *xyz;          // 3 per vertex (nv)
+    const uint32_t *tri_v;     // 3 per triangle (nt)
+    int32_t nt, nv;
+    const TriRec *tris;        // the records k_refit_tris / the upload wrote (device form)
+    // scratch, every array nt entries unless noted
+    uint32_t *cls, *order0, *key_a, *val_a, *key_b, *val_b;
+    uint32_t *table, *table_scan;   // 256 x sort_blocks
+    float4 *tri_box;                // 2 per triangle
+    int4 *rng;                      // radix-tree node: first, last, split
+    int32_t *parent, *id2, *id4, *four_of, *h_a, *h_b;
+    uint32_t *bcnt, *bbase;         // 2 per block of 256 radix-tree nodes
+    uint32_t *bpart;                // k_lbvh_classify's per-block centroid bounds (6 per block of 256 of max(nt, nv))
+    unsigned long long *bm1;        // ... and m1 bits (1 per block)
+    int32_t sort_blocks;
+    // outputs (nt entries each; slot_box 2 per slot)
+    BvhNode *nodes;
+    Bvh4F *nodes4f;
+    TriRec *leaf_recs, *always_recs;
+    uint32_t *leaf_idx, *always;
+    int32_t *tri_slot;
+    float4 *slot_box;
+    int32_t *lvl2, *lvl4;
+    LbvhStatus *status;
+};
+// The whole build on `stream`, no host round trip: classes, keys, stable radix sort, radix tree, numbering,
+// `sweeps` bottom-up box sweeps (a root they do not reach is too deep), four-wide collapse, refit tables.
+hipError_t launch_lbvh_build(const LbvhArgs &a, int sweeps, hipStream_t stream);
 // Un-permute gathered tile shards ([nranks][slots][th][tw][3], tile g of the frames x T tiles in
 // rank g % nranks, slot g / nranks) into frames x height x width x 3 bytes; with slot0 / nslots, a
 // gather chunk holding slots [slot0, slot0 + nslots) of every rank ([nranks][nslots][th][tw][3]).

@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "rt_kernels.h"
+#include "lbvh_shared.h"
 #include "spec_pow.h"
 
 namespace rt {
@@ -2871,6 +2872,539 @@ __global__ __launch_bounds__(kBlock) void k_refit_level2(BvhNode *__restrict__ n
     for (int k = 0; k < 3; ++k) { lo[k] = b.lo[k]; hi[k] = b.hi[k]; }
 }
 
+// ---- GPU BVH build: Morton-order radix tree (RT_BUILD_LBVH; host statement: bvh.cpp build_lbvh) -------
+// Rule for every kernel here: no workgroup waits on another (no spin loops, flags or last-arriver walks);
+// atomics are counters or min/max; what one launch writes, only later launches read. Kernel boundaries
+// carry the data (DESIGN.md "XCDs"), so the build has no way to hang. Launches are sized by nt and lanes
+// exit on the device-side counts in LbvhStatus.
+
+// One lane per triangle (and per vertex, for scene_m1): class, padded box, centroid bounds.
+__global__ __launch_bounds__(kBlock) void k_lbvh_classify(const LbvhArgs a) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    unsigned long long m = 0;
+    if (i < a.nv) {
+        const double v = fabs(double(a.xyz[3 * i])) + fabs(double(a.xyz[3 * i + 1])) + fabs(double(a.xyz[3 * i + 2]));
+        if (v == v) m = static_cast<unsigned long long>(__double_as_longlong(v));
+    }
+    uint32_t kmin[3] = {~0u, ~0u, ~0u}, kmax[3] = {0u, 0u, 0u};
+    if (i < a.nt) {
+        const uint32_t ia = a.tri_v[3 * i], ib = a.tri_v[3 * i + 1], ic = a.tri_v[3 * i + 2];
+        const V3 p0 = mk(a.xyz[3 * ia], a.xyz[3 * ia + 1], a.xyz[3 * ia + 2]);
+        const V3 p1 = mk(a.xyz[3 * ib], a.xyz[3 * ib + 1], a.xyz[3 * ib + 2]);
+        const V3 p2 = mk(a.xyz[3 * ic], a.xyz[3 * ic + 1], a.xyz[3 * ic + 2]);
+        const V3 u = sub(p1, p0), v = sub(p2, p0);
+        const V3 n = mk(u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x);
+        const float uu = dot(u, u), uv = dot(u, v), vv = dot(v, v);
+        const float D = uv * uv - uu * vv;
+        const float nn[3] = {n.x, n.y, n.z};
+        float lo[3], hi[3];
+        const int cls = refit_class(nn, uu, vv, D, p0, p1, p2, lo, hi);
+        a.cls[i] = static_cast<uint32_t>(cls);
+        if (cls == kTriTree) {
+            a.tri_box[2 * i] = make_float4(lo[0], lo[1], lo[2], 0.0f);
+            a.tri_box[2 * i + 1] = make_float4(hi[0], hi[1], hi[2], 0.0f);
+            for (int k = 0; k < 3; ++k) {
+                const float c = 0.5f * (lo[k] + hi[k]);   // BuildPrim::centroid
+                kmin[k] = kmax[k] = lbvh_ordered(static_cast<uint32_t>(as_int(c)));
+            }
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long x = __shfl_xor(m, o);
+        m = x > m ? x : m;
+        for (int k = 0; k < 3; ++k) {
+            const uint32_t lo = __shfl_xor(kmin[k], o), hi = __shfl_xor(kmax[k], o);
+            kmin[k] = lo < kmin[k] ? lo : kmin[k];
+            kmax[k] = hi > kmax[k] ? hi : kmax[k];
+        }
+    }
+    // per-block partials (plain stores; k_lbvh_bounds reduces them in the next launch: no atomics on one line)
+    __shared__ unsigned long long sm[kBlock / 64];
+    __shared__ uint32_t smin[kBlock / 64][3], smax[kBlock / 64][3];
+    if ((threadIdx.x & 63) == 0) {
+        sm[threadIdx.x >> 6] = m;
+        for (int k = 0; k < 3; ++k) { smin[threadIdx.x >> 6][k] = kmin[k]; smax[threadIdx.x >> 6][k] = kmax[k]; }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kBlock / 64; ++w) {
+            m = sm[w] > m ? sm[w] : m;
+            for (int k = 0; k < 3; ++k) {
+                kmin[k] = smin[w][k] < kmin[k] ? smin[w][k] : kmin[k];
+                kmax[k] = smax[w][k] > kmax[k] ? smax[w][k] : kmax[k];
+            }
+        }
+        a.bm1[blockIdx.x] = m;
+        for (int k = 0; k < 3; ++k) { a.bpart[6 * static_cast<int64_t>(blockIdx.x) + k] = kmin[k]; a.bpart[6 * static_cast<int64_t>(blockIdx.x) + 3 + k] = kmax[k]; }
+    }
+}
+
+// The blocks' partial bounds reduced by one workgroup into the status record (exact integer min / max).
+constexpr int kScanBlock = 1024;
+__global__ __launch_bounds__(kScanBlock) void k_lbvh_bounds(const LbvhArgs a, int64_t nb) {
+    __shared__ unsigned long long sm[kScanBlock / 64];
+    __shared__ uint32_t smin[kScanBlock / 64][3], smax[kScanBlock / 64][3];
+    unsigned long long m = 0;
+    uint32_t kmin[3] = {~0u, ~0u, ~0u}, kmax[3] = {0u, 0u, 0u};
+    for (int64_t b = threadIdx.x; b < nb; b += kScanBlock) {
+        const unsigned long long x = a.bm1[b];
+        m = x > m ? x : m;
+        for (int k = 0; k < 3; ++k) {
+            const uint32_t lo = a.bpart[6 * b + k], hi = a.bpart[6 * b + 3 + k];
+            kmin[k] = lo < kmin[k] ? lo : kmin[k];
+            kmax[k] = hi > kmax[k] ? hi : kmax[k];
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long x = __shfl_xor(m, o);
+        m = x > m ? x : m;
+        for (int k = 0; k < 3; ++k) {
+            const uint32_t lo = __shfl_xor(kmin[k], o), hi = __shfl_xor(kmax[k], o);
+            kmin[k] = lo < kmin[k] ? lo : kmin[k];
+            kmax[k] = hi > kmax[k] ? hi : kmax[k];
+        }
+    }
+    if ((threadIdx.x & 63) == 0) {
+        sm[threadIdx.x >> 6] = m;
+        for (int k = 0; k < 3; ++k) { smin[threadIdx.x >> 6][k] = kmin[k]; smax[threadIdx.x >> 6][k] = kmax[k]; }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kScanBlock / 64; ++w) {
+            m = sm[w] > m ? sm[w] : m;
+            for (int k = 0; k < 3; ++k) {
+                kmin[k] = smin[w][k] < kmin[k] ? smin[w][k] : kmin[k];
+                kmax[k] = smax[w][k] > kmax[k] ? smax[w][k] : kmax[k];
+            }
+        }
+        a.status->m1_bits = m;
+        for (int k = 0; k < 3; ++k) { a.status->cen_min[k] = kmin[k]; a.status->cen_max[k] = kmax[k]; }
+    }
+}
+
+// The stable split: a per-block digit histogram, a scan of the digit x block table, and a scatter with a
+// stable in-block rank. Block b owns keys [b * kLbvhSortItems, (b + 1) * kLbvhSortItems) of the first n
+// (n_ptr null: n_fixed). Run with the class as the digit it partitions tree / always / never in triangle
+// order; run four times on 8 bits of the Morton code it is the LSD radix sort.
+__global__ __launch_bounds__(kBlock) void k_lbvh_hist(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ n_ptr,
+                                                      int n_fixed, int shift, uint32_t *__restrict__ table, int nblocks) {
+    __shared__ uint32_t h[256];
+    h[threadIdx.x] = 0;
+    __syncthreads();
+    const int64_t n = n_ptr ? static_cast<int64_t>(*n_ptr) : n_fixed;
+    const int64_t base = static_cast<int64_t>(blockIdx.x) * kLbvhSortItems;
+    for (int r = 0; r < kLbvhSortItems / kBlock; ++r) {
+        const int64_t i = base + r * kBlock + threadIdx.x;
+        if (i < n) atomicAdd(&h[(keys[i] >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    table[static_cast<int64_t>(threadIdx.x) * nblocks + blockIdx.x] = h[threadIdx.x];
+}
+
+// Exclusive scan of `total` counters by one workgroup (in -> out); totals (may be null): the scanned
+// values at entries stride, 2 * stride, 3 * stride (the class split's np, np + na, nt).
+__global__ __launch_bounds__(kScanBlock) void k_lbvh_scan(const uint32_t *__restrict__ in, uint32_t *__restrict__ out, int64_t total,
+                                                           uint32_t *totals, int64_t stride) {
+    __shared__ uint32_t sums[kScanBlock];
+    const int64_t per = (total + kScanBlock - 1) / kScanBlock;
+    const int64_t b = per * threadIdx.x, e = b + per < total ? b + per : total;
+    uint32_t s = 0;
+    for (int64_t i = b; i < e; ++i) s += in[i];
+    sums[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 1; o < kScanBlock; o <<= 1) {
+        const uint32_t add = static_cast<int>(threadIdx.x) >= o ? sums[threadIdx.x - o] : 0u;
+        __syncthreads();
+        sums[threadIdx.x] += add;
+        __syncthreads();
+    }
+    uint32_t acc = sums[threadIdx.x] - s;   // exclusive
+    for (int64_t i = b; i < e; ++i) {
+        const uint32_t c = in[i];
+        out[i] = acc;
+        if (totals && i > 0 && i % stride == 0 && i / stride <= 3) totals[i / stride - 1] = acc;
+        acc += c;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_lbvh_scatter(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ vals,
+                                                         uint32_t *__restrict__ keys_out, uint32_t *__restrict__ vals_out,
+                                                         const uint32_t *__restrict__ n_ptr, int n_fixed, int cap, int shift,
+                                                         const uint32_t *__restrict__ offs, int nblocks) {
+    __shared__ uint32_t base[256], wc[kBlock / 64][256];
+    base[threadIdx.x] = offs[static_cast<int64_t>(threadIdx.x) * nblocks + blockIdx.x];
+    const int64_t n = n_ptr ? static_cast<int64_t>(*n_ptr) : n_fixed;
+    const int64_t first = static_cast<int64_t>(blockIdx.x) * kLbvhSortItems;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int r = 0; r < kLbvhSortItems / kBlock; ++r) {   // block-uniform
+        if (first + r * kBlock >= n) break;
+        for (int w = 0; w < kBlock / 64; ++w) wc[w][threadIdx.x] = 0;
+        __syncthreads();
+        const int64_t i = first + r * kBlock + threadIdx.x;
+        const bool valid = i < n;
+        const uint32_t key = valid ? keys[i] : 0u;
+        const uint32_t d = (key >> shift) & 255u;
+        unsigned long long same = __ballot(valid);
+        for (int bit = 0; bit < 8; ++bit) {
+            const bool on = ((d >> bit) & 1u) != 0;
+            const unsigned long long bal = __ballot(valid && on);
+            same &= on ? bal : ~bal;
+        }
+        const int rank = __popcll(same & ((1ull << lane) - 1ull));
+        if (valid && rank == 0) wc[wave][d] = static_cast<uint32_t>(__popcll(same));
+        __syncthreads();
+        if (valid) {
+            uint32_t pos = base[d] + static_cast<uint32_t>(rank);
+            for (int w = 0; w < wave; ++w) pos += wc[w][d];
+            if (pos < static_cast<uint32_t>(cap)) {
+                keys_out[pos] = key;
+                vals_out[pos] = vals ? vals[i] : static_cast<uint32_t>(i);
+            }
+        }
+        __syncthreads();
+        uint32_t add = 0;
+        for (int w = 0; w < kBlock / 64; ++w) add += wc[w][threadIdx.x];
+        base[threadIdx.x] += add;
+        __syncthreads();
+    }
+}
+
+// One lane per tree triangle (in triangle order): its Morton code.
+__global__ __launch_bounds__(kBlock) void k_lbvh_codes(const LbvhArgs a) {
+    const int64_t j = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (j >= a.status->np) return;
+    const uint32_t t = a.order0[j];
+    if (t >= static_cast<uint32_t>(a.nt)) { a.status->error = 1; return; }
+    const float4 l = a.tri_box[2 * static_cast<int64_t>(t)], h = a.tri_box[2 * static_cast<int64_t>(t) + 1];
+    const float lo[3] = {l.x, l.y, l.z}, hi[3] = {h.x, h.y, h.z};
+    uint32_t q[3];
+    for (int k = 0; k < 3; ++k) {
+        const float c = 0.5f * (lo[k] + hi[k]);
+        const float cmin = as_float(static_cast<int>(lbvh_unordered(a.status->cen_min[k])));
+        const float cmax = as_float(static_cast<int>(lbvh_unordered(a.status->cen_max[k])));
+        q[k] = lbvh_cell(c, cmin, cmax);
+    }
+    a.key_a[j] = lbvh_code(q[0], q[1], q[2]);
+    a.val_a[j] = t;
+}
+
+// Karras' construction: one lane per radix-tree node, no atomics.
+__global__ __launch_bounds__(kBlock) void k_lbvh_topo(const LbvhArgs a) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    const int32_t np = static_cast<int32_t>(a.status->np);
+    if (i >= np - 1) return;
+    const LbvhRange r = lbvh_node(a.key_a, np, static_cast<int32_t>(i));
+    a.rng[i] = make_int4(r.first, r.last, r.split, 0);
+    if (r.split != r.first) a.parent[r.split] = static_cast<int32_t>(i);
+    if (r.split + 1 != r.last) a.parent[r.split + 1] = static_cast<int32_t>(i);
+}
+
+// One lane per triangle, by its place in the class split: leaf slot p (the sorted order), always-list
+// entry p - np, or never accepted. Records are gathered from the d_tris k_refit_tris (or the upload) wrote.
+__global__ __launch_bounds__(kBlock) void k_lbvh_gather(const LbvhArgs a) {
+    const int64_t p = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (p >= a.nt) return;
+    const int64_t np = a.status->np, np_na = a.status->np_na;
+    if ((p < np ? a.val_a[p] : a.order0[p]) >= static_cast<uint32_t>(a.nt)) { a.status->error = 1; return; }
+    if (p < np) {
+        const uint32_t t = a.val_a[p];
+        const float4 *src = reinterpret_cast<const float4 *>(a.tris + t);
+        float4 *dst = reinterpret_cast<float4 *>(a.leaf_recs + p);
+        dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2]; dst[3] = src[3];
+        a.leaf_idx[p] = t;
+        a.slot_box[2 * p] = a.tri_box[2 * static_cast<int64_t>(t)];
+        a.slot_box[2 * p + 1] = a.tri_box[2 * static_cast<int64_t>(t) + 1];
+        a.tri_slot[t] = static_cast<int32_t>(p);
+    } else if (p < np_na) {
+        const uint32_t t = a.order0[p];
+        const int64_t k = p - np;
+        const float4 *src = reinterpret_cast<const float4 *>(a.tris + t);
+        float4 *dst = reinterpret_cast<float4 *>(a.always_recs + k);
+        dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2]; dst[3] = src[3];
+        a.always[k] = t;
+        a.tri_slot[t] = -1 - static_cast<int32_t>(k);
+    } else {
+        a.tri_slot[a.order0[p]] = kRefitNeverSlot;
+    }
+}
+
+// One lane per radix-tree node: its depth (a walk up the parents the launch before wrote), whether it is
+// emitted as a binary node (more than RT_BVH_MAX_LEAF triangles) and as a four-wide node (emitted, even
+// depth); per block of 256 the two counts, for the numbering.
+__global__ __launch_bounds__(kBlock) void k_lbvh_flags(const LbvhArgs a) {
+    __shared__ uint32_t c2[kBlock / 64], c4[kBlock / 64];
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    const int32_t np = static_cast<int32_t>(a.status->np);
+    bool e2 = false, e4 = false;
+    uint32_t md = 0, me = 0;
+    if (i < np - 1) {
+        int32_t d = 0;
+        for (int32_t p = a.parent[i]; p >= 0 && d <= kMaxBvhDepth; p = a.parent[p]) ++d;
+        const int4 r = a.rng[i];
+        e2 = r.y - r.x + 1 > RT_BVH_MAX_LEAF;
+        e4 = e2 && (d & 1) == 0;
+        if (e2) md = static_cast<uint32_t>(d);
+        if (e4) me = static_cast<uint32_t>(d);
+    }
+    const unsigned long long b2 = __ballot(e2), b4 = __ballot(e4);
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t x = __shfl_xor(md, o), y = __shfl_xor(me, o);
+        md = x > md ? x : md;
+        me = y > me ? y : me;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        c2[threadIdx.x >> 6] = static_cast<uint32_t>(__popcll(b2));
+        c4[threadIdx.x >> 6] = static_cast<uint32_t>(__popcll(b4));
+        if (md) atomicMax(&a.status->max_depth, md);
+        if (me) atomicMax(&a.status->max_even, me);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t s2 = 0, s4 = 0;
+        for (int w = 0; w < kBlock / 64; ++w) { s2 += c2[w]; s4 += c4[w]; }
+        a.bcnt[2 * static_cast<int64_t>(blockIdx.x)] = s2;
+        a.bcnt[2 * static_cast<int64_t>(blockIdx.x) + 1] = s4;
+    }
+}
+
+// Exclusive scan of the per-block count pairs by one workgroup; the totals are n2 and n4.
+__global__ __launch_bounds__(kScanBlock) void k_lbvh_idscan(const LbvhArgs a, int64_t nb) {
+    __shared__ uint32_t s2[kScanBlock], s4[kScanBlock];
+    const int64_t per = (nb + kScanBlock - 1) / kScanBlock;
+    const int64_t b = per * threadIdx.x, e = b + per < nb ? b + per : nb;
+    uint32_t t2 = 0, t4 = 0;
+    for (int64_t i = b; i < e; ++i) { t2 += a.bcnt[2 * i]; t4 += a.bcnt[2 * i + 1]; }
+    s2[threadIdx.x] = t2;
+    s4[threadIdx.x] = t4;
+    __syncthreads();
+    for (int o = 1; o < kScanBlock; o <<= 1) {
+        const bool on = static_cast<int>(threadIdx.x) >= o;
+        const uint32_t x = on ? s2[threadIdx.x - o] : 0u, y = on ? s4[threadIdx.x - o] : 0u;
+        __syncthreads();
+        s2[threadIdx.x] += x;
+        s4[threadIdx.x] += y;
+        __syncthreads();
+    }
+    uint32_t a2 = s2[threadIdx.x] - t2, a4 = s4[threadIdx.x] - t4;
+    for (int64_t i = b; i < e; ++i) {
+        a.bbase[2 * i] = a2;
+        a.bbase[2 * i + 1] = a4;
+        a2 += a.bcnt[2 * i];
+        a4 += a.bcnt[2 * i + 1];
+    }
+    if (threadIdx.x == kScanBlock - 1) { a.status->n2 = s2[threadIdx.x]; a.status->n4 = s4[threadIdx.x]; }
+}
+
+// Ids by prefix sum in radix-tree node order (the root, node 0, gets id 0 in both trees).
+__global__ __launch_bounds__(kBlock) void k_lbvh_ids(const LbvhArgs a) {
+    __shared__ uint32_t c2[kBlock / 64], c4[kBlock / 64];
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    const int32_t np = static_cast<int32_t>(a.status->np);
+    bool e2 = false, e4 = false;
+    if (i < np - 1) {
+        int32_t d = 0;
+        for (int32_t p = a.parent[i]; p >= 0 && d <= kMaxBvhDepth; p = a.parent[p]) ++d;
+        const int4 r = a.rng[i];
+        e2 = r.y - r.x + 1 > RT_BVH_MAX_LEAF;
+        e4 = e2 && (d & 1) == 0;
+    }
+    const unsigned long long b2 = __ballot(e2), b4 = __ballot(e4);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) { c2[wave] = static_cast<uint32_t>(__popcll(b2)); c4[wave] = static_cast<uint32_t>(__popcll(b4)); }
+    __syncthreads();
+    if (i >= np - 1) return;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    uint32_t r2 = a.bbase[2 * static_cast<int64_t>(blockIdx.x)] + static_cast<uint32_t>(__popcll(b2 & below));
+    uint32_t r4 = a.bbase[2 * static_cast<int64_t>(blockIdx.x) + 1] + static_cast<uint32_t>(__popcll(b4 & below));
+    for (int w = 0; w < wave; ++w) { r2 += c2[w]; r4 += c4[w]; }
+    a.id2[i] = e2 ? static_cast<int32_t>(r2) : -1;
+    a.id4[i] = e4 ? static_cast<int32_t>(r4) : -1;
+}
+
+// The binary nodes' child refs (boxes come from the sweeps) and each one's four-wide id.
+__global__ __launch_bounds__(kBlock) void k_lbvh_nodes2(const LbvhArgs a) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    const int32_t np = static_cast<int32_t>(a.status->np);
+    if (i >= np - 1) return;
+    const int32_t id = a.id2[i];
+    if (id < 0 || id >= a.nt) return;
+    const int4 r = a.rng[i];
+    int32_t ref[2];
+    for (int side = 0; side < 2; ++side) {
+        const int32_t f = side ? r.z + 1 : r.x, l = side ? r.y : r.z, inner = side ? r.z + 1 : r.z;
+        if (l - f + 1 > RT_BVH_MAX_LEAF) {
+            ref[side] = a.id2[inner];
+            if (ref[side] < 0 || ref[side] >= a.nt) { ref[side] = kBvhEmpty; a.status->error = 1; }
+        } else {
+            ref[side] = static_cast<int32_t>(kBvhLeafBit | (static_cast<uint32_t>(l - f + 1) << kBvhCountShift) | static_cast<uint32_t>(f));
+        }
+    }
+    float4 *g = reinterpret_cast<float4 *>(a.nodes + id);
+    g[0] = make_float4(0, 0, 0, 0); g[1] = g[0]; g[2] = g[0];
+    g[3] = make_float4(as_float(ref[0]), as_float(ref[1]), 0.0f, 0.0f);
+    a.four_of[id] = a.id4[i];
+}
+
+// One bottom-up sweep: every binary node not yet finished whose children were finished by an earlier
+// sweep writes its two child boxes (each the exact union of what lies below that child, k_refit_level2's
+// statement) and records its height k. Heights are read from h_in and written to h_out, so the launch
+// reads nothing it writes.
+__global__ __launch_bounds__(kBlock) void k_lbvh_sweep(const LbvhArgs a, const int32_t *__restrict__ h_in, int32_t *__restrict__ h_out,
+                                                       int k) {
+    const int64_t id = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    bool fin = false, fin4 = false;
+    do {
+        if (id >= a.status->n2 || id >= a.nt) break;
+        const int32_t h = h_in[id];
+        if (h >= 0) { h_out[id] = h; break; }
+        const BvhNode &n = a.nodes[id];
+        const int32_t c0 = n.c0, c1 = n.c1;
+        const bool l0 = (static_cast<uint32_t>(c0) & kBvhLeafBit) != 0, l1 = (static_cast<uint32_t>(c1) & kBvhLeafBit) != 0;
+        if (!((l0 || h_in[c0] >= 0) && (l1 || h_in[c1] >= 0))) { h_out[id] = -1; break; }
+        for (int side = 0; side < 2; ++side) {
+            const int32_t ref = side ? c1 : c0;
+            if (ref == kBvhEmpty) continue;
+            RBox b;
+            if (static_cast<uint32_t>(ref) & kBvhLeafBit) {
+                b = leaf_union(ref, a.slot_box);
+            } else {
+                b = RBox{{FLT_MAX, FLT_MAX, FLT_MAX}, {-FLT_MAX, -FLT_MAX, -FLT_MAX}};
+                const BvhNode &g = a.nodes[ref];
+                if (g.c0 != kBvhEmpty) rgrow(b, g.lo0, g.hi0);
+                if (g.c1 != kBvhEmpty) rgrow(b, g.lo1, g.hi1);
+            }
+            float *lo = side ? a.nodes[id].lo1 : a.nodes[id].lo0, *hi = side ? a.nodes[id].hi1 : a.nodes[id].hi0;
+            for (int c = 0; c < 3; ++c) { lo[c] = b.lo[c]; hi[c] = b.hi[c]; }
+        }
+        h_out[id] = k;
+        fin = true;
+        fin4 = a.four_of[id] >= 0;
+    } while (false);
+    // the per-height counts, one atomic per wave
+    const unsigned long long b2 = __ballot(fin), b4 = __ballot(fin4);
+    if ((threadIdx.x & 63) == 0) {
+        if (b2) atomicAdd(&a.status->cnt2[k], static_cast<uint32_t>(__popcll(b2)));
+        if (b4) atomicAdd(&a.status->cnt4[k >> 1], static_cast<uint32_t>(__popcll(b4)));
+    }
+}
+
+// One lane: whether the sweeps reached the root, the per-height offsets of the refit tables, and the
+// trees of at most RT_BVH_MAX_LEAF triangles (an empty root, or one leaf wrapped in a root, as build_bvh).
+__global__ void k_lbvh_levels(const LbvhArgs a, const int32_t *__restrict__ h_fin) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    LbvhStatus &s = *a.status;
+    const uint32_t np = s.np;
+    if (np <= RT_BVH_MAX_LEAF) {
+        BvhNode root{};
+        Bvh4F g{};
+        for (int k = 0; k < 3; ++k) {
+            root.lo0[k] = root.lo1[k] = FLT_MAX; root.hi0[k] = root.hi1[k] = -FLT_MAX;
+            for (int c = 0; c < 4; ++c) { g.lo[k][c] = INFINITY; g.hi[k][c] = -INFINITY; }
+        }
+        root.c0 = root.c1 = kBvhEmpty;
+        for (int c = 0; c < 4; ++c) g.child[c] = kBvhEmpty;
+        if (np > 0) {
+            root.c0 = static_cast<int32_t>(kBvhLeafBit | (np << kBvhCountShift));
+            const RBox b = leaf_union(root.c0, a.slot_box);
+            g.child[0] = root.c0;
+            for (int k = 0; k < 3; ++k) { root.lo0[k] = g.lo[k][0] = b.lo[k]; root.hi0[k] = g.hi[k][0] = b.hi[k]; }
+        }
+        a.nodes[0] = root;
+        a.nodes4f[0] = g;
+        a.lvl2[0] = 0;
+        a.lvl4[0] = 0;
+        s.n2 = s.n4 = 1;
+        s.root_done = 1;
+        s.off2[0] = s.off4[0] = 0;
+        for (int h = 1; h <= kLbvhHeights; ++h) s.off2[h] = s.off4[h] = 1;
+        return;
+    }
+    s.root_done = h_fin[0] >= 0 ? 1u : 0u;
+    uint32_t o2 = 0, o4 = 0;
+    for (int h = 0; h < kLbvhHeights; ++h) {
+        s.off2[h] = s.cur2[h] = o2;
+        s.off4[h] = s.cur4[h] = o4;
+        o2 += s.cnt2[h];
+        o4 += s.cnt4[h];
+    }
+    s.off2[kLbvhHeights] = o2;
+    s.off4[kLbvhHeights] = o4;
+}
+
+// The four-wide tree: one lane per binary node that is also a four-wide node (even depth). Its children
+// are its grandchildren, or a child that is a leaf, in order, with the boxes the sweeps left in the binary
+// nodes; unused slots are inverted boxes with kBvhEmpty (make_node4f).
+__global__ __launch_bounds__(kBlock) void k_lbvh_emit4(const LbvhArgs a) {
+    const int64_t id = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (a.status->np <= RT_BVH_MAX_LEAF || id >= a.status->n2 || id >= a.nt) return;
+    const int32_t f = a.four_of[id];
+    if (f < 0 || f >= a.nt) return;
+    // candidates in order [child 0's children | child 0, -] [child 1's children | child 1, -]; only slots 1
+    // and 3 can be absent, so compaction is one shift (static indexing: everything stays in registers)
+    struct Cand { int32_t ref; float lo[3], hi[3]; };
+    const Cand none{kBvhEmpty, {INFINITY, INFINITY, INFINITY}, {-INFINITY, -INFINITY, -INFINITY}};
+    Cand c[4] = {none, none, none, none};
+    const BvhNode &n = a.nodes[id];
+#pragma unroll
+    for (int side = 0; side < 2; ++side) {
+        const int32_t r = side ? n.c1 : n.c0;
+        if (static_cast<uint32_t>(r) & kBvhLeafBit) {
+            c[2 * side].ref = r;
+            for (int k = 0; k < 3; ++k) { c[2 * side].lo[k] = side ? n.lo1[k] : n.lo0[k]; c[2 * side].hi[k] = side ? n.hi1[k] : n.hi0[k]; }
+            continue;
+        }
+        const BvhNode &m = a.nodes[r];
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+            int32_t q = s2 ? m.c1 : m.c0;
+            if (!(static_cast<uint32_t>(q) & kBvhLeafBit)) {
+                q = a.four_of[q];
+                if (q < 0 || q >= a.nt) { q = kBvhEmpty; a.status->error = 1; }
+            }
+            c[2 * side + s2].ref = q;
+            for (int k = 0; k < 3; ++k) { c[2 * side + s2].lo[k] = s2 ? m.lo1[k] : m.lo0[k]; c[2 * side + s2].hi[k] = s2 ? m.hi1[k] : m.hi0[k]; }
+        }
+    }
+    if (static_cast<uint32_t>(n.c0) & kBvhLeafBit) { c[1] = c[2]; c[2] = c[3]; c[3] = none; }
+    float4 *g = reinterpret_cast<float4 *>(a.nodes4f + f);
+    for (int k = 0; k < 3; ++k) {
+        g[k] = make_float4(c[0].lo[k], c[1].lo[k], c[2].lo[k], c[3].lo[k]);
+        g[3 + k] = make_float4(c[0].hi[k], c[1].hi[k], c[2].hi[k], c[3].hi[k]);
+    }
+    g[6] = make_float4(as_float(c[0].ref), as_float(c[1].ref), as_float(c[2].ref), as_float(c[3].ref));
+    g[7] = make_float4(0, 0, 0, 0);
+}
+
+// The refit's level tables: node ids grouped by height (four-wide nodes by height / 2: a four-wide
+// child is a binary grandchild, so its group is lower). Order inside a group is free.
+__global__ __launch_bounds__(kBlock) void k_lbvh_tables(const LbvhArgs a, const int32_t *__restrict__ h_fin) {
+    const int64_t id = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    const bool in = a.status->np > RT_BVH_MAX_LEAF && id < a.status->n2 && id < a.nt;
+    int32_t h = in ? h_fin[id] : -1;
+    if (h >= kLbvhHeights) h = -1;
+    const int32_t f = h >= 0 ? a.four_of[id] : -1;
+    const int lane = threadIdx.x & 63;
+    // lanes of a wave with the same height share one cursor step (the lanes found by ballots, as in the
+    // scatter); every lane runs the ballots and the shuffle
+    for (int tree = 0; tree < 2; ++tree) {
+        const bool v = tree ? f >= 0 : h >= 0;
+        const int32_t key = tree ? h >> 1 : h;
+        unsigned long long same = __ballot(v);
+        for (int bit = 0; bit < 6; ++bit) {
+            const bool on = ((key >> bit) & 1) != 0;
+            const unsigned long long bal = __ballot(v && on);
+            same &= on ? bal : ~bal;
+        }
+        const int leader = v ? __ffsll(static_cast<long long>(same)) - 1 : lane;
+        uint32_t base = 0;
+        if (v && lane == leader) base = atomicAdd(tree ? &a.status->cur4[key] : &a.status->cur2[key], static_cast<uint32_t>(__popcll(same)));
+        base = __shfl(base, leader);
+        if (!v) continue;
+        const uint32_t pos = base + static_cast<uint32_t>(__popcll(same & ((1ull << lane) - 1ull)));
+        if (pos < static_cast<uint32_t>(a.nt)) (tree ? a.lvl4 : a.lvl2)[pos] = tree ? f : static_cast<int32_t>(id);
+    }
+}
+
 // rayIntersectTriangle (raytracing.cpp:99-154) for n independent (ray, triangle) pairs, every
 // step in the reference's order; unlike intersectMesh's use of it there is no distance compare, so
 // a hit whose point is NaN or infinite is still reported, as the reference returns true for it.
@@ -3388,6 +3922,52 @@ void launch_refit_tris(const RefitArgs &a, hipStream_t stream) {
     const int64_t n = std::max<int64_t>(a.nt, a.nv);
     if (n <= 0) return;
     hipLaunchKernelGGL(k_refit_tris, dim3(grid_for(n)), dim3(kBlock), 0, stream, a);
+}
+
+hipError_t launch_lbvh_build(const LbvhArgs &a, int sweeps, hipStream_t st) {
+    const int64_t nt = a.nt, cap = std::max<int64_t>(nt, 1);
+    const unsigned g_tri = grid_for(std::max<int64_t>(std::max<int64_t>(nt, a.nv), 1)), g_nt = grid_for(cap);
+    const unsigned g_sort = static_cast<unsigned>(a.sort_blocks);
+    hipError_t e = hipMemsetAsync(a.status, 0, sizeof(LbvhStatus), st);
+    if (e == hipSuccess) e = hipMemsetAsync(a.parent, 0xFF, sizeof(int32_t) * cap, st);
+    if (e == hipSuccess) e = hipMemsetAsync(a.h_a, 0xFF, sizeof(int32_t) * cap, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_lbvh_classify, dim3(g_tri), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(k_lbvh_bounds, dim3(1), dim3(kScanBlock), 0, st, a, static_cast<int64_t>(g_tri));
+    // tree / always / never in triangle order: the split on the class
+    const int64_t table = 256 * static_cast<int64_t>(a.sort_blocks);
+    hipLaunchKernelGGL(k_lbvh_hist, dim3(g_sort), dim3(kBlock), 0, st, a.cls, nullptr, a.nt, 0, a.table, a.sort_blocks);
+    hipLaunchKernelGGL(k_lbvh_scan, dim3(1), dim3(kScanBlock), 0, st, a.table, a.table_scan, table, &a.status->np,
+                       static_cast<int64_t>(a.sort_blocks));
+    hipLaunchKernelGGL(k_lbvh_scatter, dim3(g_sort), dim3(kBlock), 0, st, a.cls, nullptr, a.key_b, a.order0, nullptr, a.nt,
+                       static_cast<int>(cap), 0, a.table_scan, a.sort_blocks);
+    hipLaunchKernelGGL(k_lbvh_codes, dim3(g_nt), dim3(kBlock), 0, st, a);
+    // stable LSD radix sort of (code, triangle): four 8-bit passes, a -> b -> a -> b -> a
+    for (int pass = 0; pass < 4; ++pass) {
+        const uint32_t *ki = (pass & 1) ? a.key_b : a.key_a, *vi = (pass & 1) ? a.val_b : a.val_a;
+        uint32_t *ko = (pass & 1) ? a.key_a : a.key_b, *vo = (pass & 1) ? a.val_a : a.val_b;
+        hipLaunchKernelGGL(k_lbvh_hist, dim3(g_sort), dim3(kBlock), 0, st, ki, &a.status->np, 0, 8 * pass, a.table, a.sort_blocks);
+        hipLaunchKernelGGL(k_lbvh_scan, dim3(1), dim3(kScanBlock), 0, st, a.table, a.table_scan, table, nullptr, int64_t(1));
+        hipLaunchKernelGGL(k_lbvh_scatter, dim3(g_sort), dim3(kBlock), 0, st, ki, vi, ko, vo, &a.status->np, 0, static_cast<int>(cap),
+                           8 * pass, a.table_scan, a.sort_blocks);
+    }
+    hipLaunchKernelGGL(k_lbvh_topo, dim3(g_nt), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(k_lbvh_gather, dim3(g_nt), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(k_lbvh_flags, dim3(g_nt), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(k_lbvh_idscan, dim3(1), dim3(kScanBlock), 0, st, a, static_cast<int64_t>(g_nt));
+    hipLaunchKernelGGL(k_lbvh_ids, dim3(g_nt), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(k_lbvh_nodes2, dim3(g_nt), dim3(kBlock), 0, st, a);
+    const int32_t *h_fin = a.h_a;
+    for (int k = 0; k < sweeps; ++k) {   // one launch per height: the kernel boundary carries the boxes
+        const int32_t *h_in = (k & 1) ? a.h_b : a.h_a;
+        int32_t *h_out = (k & 1) ? a.h_a : a.h_b;
+        hipLaunchKernelGGL(k_lbvh_sweep, dim3(g_nt), dim3(kBlock), 0, st, a, h_in, h_out, k);
+        h_fin = h_out;
+    }
+    hipLaunchKernelGGL(k_lbvh_levels, dim3(1), dim3(64), 0, st, a, h_fin);
+    hipLaunchKernelGGL(k_lbvh_emit4, dim3(g_nt), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(k_lbvh_tables, dim3(g_nt), dim3(kBlock), 0, st, a, h_fin);
+    return hipGetLastError();
 }
 
 void launch_refit_level4(Bvh4F *nodes, const int32_t *ids, int32_t n, const float4 *slot_box, hipStream_t stream) {
