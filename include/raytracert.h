@@ -368,6 +368,11 @@ int rt_scene_bvh_info(rt_scene *scene, int32_t info[RT_BVH_INFO_FIELDS]);
 /* 64-bit FNV-1a digest of the BVH arrays the device receives (both trees, leaf order, always
  * list): equal digests = identical trees (the parallel and sequential builds are compared so). */
 int rt_scene_bvh_digest(rt_scene *scene, uint64_t *digest);
+/* The order the builder chose, read only: leaf_tris[i] = the triangle in leaf slot i (info[4] entries),
+ * always[k] = the k-th always-tested triangle (info[2] entries). The counts are written whenever the
+ * pointers are valid; RT_E_ARG on a NULL pointer or a capacity below its count (nothing is copied). */
+int rt_scene_bvh_order(rt_scene *scene, uint32_t *leaf_tris, int64_t leaf_capacity, int64_t *n_leaf, uint32_t *always,
+                       int64_t always_capacity, int64_t *n_always);
 /* Host-side structural check of the built BVH (containment, coverage, depth bound). */
 int rt_scene_bvh_validate(rt_scene *scene);
 /* The padded acceptance box of one triangle T = {T0, T1, T2} (9 floats), as the BVH uses it.

@@ -151,6 +151,7 @@ _SIGNATURES = {
     "rt_batch_durations": ([_VP, _VP, C.c_int64, C.POINTER(C.c_int64)], C.c_int),
     "rt_scene_trials": ([_VP, _VP, _VP], C.c_int),
     "rt_scene_bvh_digest": ([_VP, C.POINTER(C.c_uint64)], C.c_int),
+    "rt_scene_bvh_order": ([_VP, _VP, C.c_int64, C.POINTER(C.c_int64), _VP, C.c_int64, C.POINTER(C.c_int64)], C.c_int),
     "rt_scene_bvh_validate": ([_VP], C.c_int),
     "rt_bvh_acceptance_box": ([_VP, _VP, _VP], C.c_int),
     "rt_scene_tune": ([_VP, C.c_int32, C.c_int32], C.c_int),

@@ -458,6 +458,16 @@ class Scene:
         check(lib().rt_scene_bvh_digest(self._h, C.byref(d)))
         return d.value
 
+    def bvh_order(self) -> tuple[np.ndarray, np.ndarray]:
+        """rt_scene_bvh_order: (the triangle index of each leaf slot, the always-tested triangles), uint32."""
+        info = self.bvh_info()
+        leaf = np.zeros(max(info["leaf_triangles"], 1), np.uint32)
+        always = np.zeros(max(info["always"], 1), np.uint32)
+        nl, na = C.c_int64(), C.c_int64()
+        check(lib().rt_scene_bvh_order(self._h, _ptr(leaf), info["leaf_triangles"], C.byref(nl), _ptr(always), info["always"],
+                                       C.byref(na)))
+        return leaf[:nl.value].copy(), always[:na.value].copy()
+
     def bvh_validate(self) -> None:
         check(lib().rt_scene_bvh_validate(self._h))
 
