@@ -189,16 +189,27 @@ int  rt_scene_update_vertices_device(rt_scene *scene, const void *d_xyz, int32_t
  * no host build and no upload; on a host-only scene the same tree is built on the CPU. A tree that
  * would break a limit of the traversal (more than 40 levels, the leaf index field, boxes that cannot
  * be quantised) is built by the SAH builder instead, without an error.
+ * RT_BUILD_CLUSTER is an agglomerative builder (parallel locally-ordered clustering, Meister & Bittner
+ * 2018): it keeps the Morton builder's leaf order and replaces the radix tree by nearest-neighbour merges
+ * on the surface area of the union box, so that a few huge triangles no longer inflate the upper boxes.
+ * On a device scene HIP kernels build it from the device-resident vertices, on a host-only scene the CPU
+ * builds the same arrays bit for bit. A tree that would break a limit (depth, leaf index field, boxes that
+ * cannot be quantised), or a clustering that does not finish within its iteration budget, is built by
+ * the Morton builder instead (which keeps its own fallback to SAH), without an error: built_with and the
+ * update's outcome report the builder that made the trees (rt_scene_build_info reports why).
  * rt_scene_set_builder rebuilds nothing: it chooses the builder of the scene's later builds
  * (RT_UPDATE_REBUILD, RT_UPDATE_AUTO's rebuild after a class change, a lazy first build). RT_E_ARG
  * (scene untouched) for an unknown value. rt_scene_get_builder reports the chosen builder and the one
  * that built the trees the scene holds now (either pointer may be NULL).
  * *outcome of rt_scene_update_vertices[_device] is RT_UPDATED_REBUILT_LBVH when the Morton-order
- * builder made the new trees; RT_UPDATED_REBUILT keeps meaning the host SAH build.
+ * builder made the new trees and RT_UPDATED_REBUILT_CLUSTER when the agglomerative one did;
+ * RT_UPDATED_REBUILT keeps meaning the host SAH build.
  * rt_scene_create_ex is rt_scene_create with the builder of the scene's first trees. */
 #define RT_BUILD_SAH   0
 #define RT_BUILD_LBVH  1
+#define RT_BUILD_CLUSTER 2
 #define RT_UPDATED_REBUILT_LBVH 2
+#define RT_UPDATED_REBUILT_CLUSTER 3
 int  rt_scene_set_builder(rt_scene *scene, int32_t builder);
 int  rt_scene_get_builder(const rt_scene *scene, int32_t *selected, int32_t *built_with);
 int  rt_scene_create_ex(const float *xyz, int32_t n_vertices, const uint32_t *tri_v, const uint32_t *tri_mat,

@@ -120,8 +120,9 @@ class RayTracer {
                                        rebuild ? RT_UPDATE_REBUILD : RT_UPDATE_AUTO, &outcome));
         return outcome == RT_UPDATED_REFIT;
     }
-    // The builder of later rebuilds (rt_scene_set_builder): RT_BUILD_SAH (the default) or RT_BUILD_LBVH, the
-    // Morton-order tree built on the GPU; same results, a far cheaper rebuild, somewhat slower frames.
+    // The builder of later rebuilds (rt_scene_set_builder): RT_BUILD_SAH (the default), RT_BUILD_LBVH, the
+    // Morton-order tree built on the GPU (same results, a far cheaper rebuild, somewhat slower frames), or
+    // RT_BUILD_CLUSTER, the agglomerative tree built on the GPU (a little dearer to build, faster frames).
     void setBuilder(int32_t builder) { check(rt_scene_set_builder(scene_, builder)); }
 
     // getMaterial(int), raytracing.cpp:373-376

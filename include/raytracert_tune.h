@@ -195,6 +195,22 @@ int rt_workspace_bytes(rt_scene *s, uint64_t *bytes, uint64_t *multi_frame_fallb
 int rt_workspace_layout(int64_t cap, int32_t steps, int32_t lights, uint64_t *total_bytes,
                         uint64_t extents[2 * RT_WS_ARRAYS]);
 
+/* How the scene's current trees were built (builds them first if the scene has none yet), for comparing
+ * the builders on any machine: info = {[0] the builder that made them (RT_BUILD_*), [1] the clustering
+ * iterations it took (0 for the other builders), [2] why the last build fell back from the selected
+ * builder (RT_FALLBACK_*), [3] the clustering window radius, [4] the cluster count at or below which one
+ * workgroup finishes the clustering, [5] the iteration budget}.
+ * *cost (may be NULL), for any builder: the sum over the binary tree's inner nodes, in node order and in
+ * binary64, of the half-areas dx*dy + dy*dz + dz*dx of both child boxes, divided by the half-area of the
+ * union of the root's child boxes; computed on the host mirror (a device scene's trees are read back). */
+#define RT_BUILD_INFO_FIELDS 6
+#define RT_FALLBACK_NONE       0
+#define RT_FALLBACK_DEPTH      1   /* deeper than the traversal's stack bound */
+#define RT_FALLBACK_LEAF_INDEX 2   /* 2^21 or more tree triangles */
+#define RT_FALLBACK_BUDGET     3   /* the iteration budget ended with more than one cluster */
+#define RT_FALLBACK_QUANTISE   4   /* boxes no 8-bit grid can bound */
+#define RT_FALLBACK_DEVICE     5   /* the device build's error flag */
+int rt_scene_build_info(rt_scene *scene, int32_t info[RT_BUILD_INFO_FIELDS], double *cost);
 
 #ifdef __cplusplus
 }

@@ -64,8 +64,11 @@ WORK_FIELDS = 6
 UPDATE_AUTO, UPDATE_REBUILD = 0, 1      # rt_scene_update_vertices modes
 UPDATED_REFIT, UPDATED_REBUILT = 0, 1   # ... and outcomes
 UPDATED_REBUILT_LBVH = 2                # ... the trees rebuilt by the Morton-order builder
-BUILD_SAH, BUILD_LBVH = 0, 1            # rt_scene_set_builder
-BUILDERS = ("sah", "lbvh")
+UPDATED_REBUILT_CLUSTER = 3             # ... by the agglomerative builder
+BUILD_SAH, BUILD_LBVH, BUILD_CLUSTER = 0, 1, 2   # rt_scene_set_builder
+BUILDERS = ("sah", "lbvh", "cluster")
+BUILD_INFO_FIELDS = 6
+FALLBACK_REASONS = ("none", "depth", "leaf_index", "budget", "quantise", "device")   # RT_FALLBACK_*
 
 
 class RtParams(C.Structure):
@@ -115,6 +118,7 @@ _SIGNATURES = {
     "rt_scene_create_ex": ([_VP, C.c_int32, _VP, _VP, C.c_int32, _VP, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_VP)], C.c_int),
     "rt_scene_set_builder": ([_VP, C.c_int32], C.c_int),
     "rt_scene_get_builder": ([_VP, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], C.c_int),
+    "rt_scene_build_info": ([_VP, C.POINTER(C.c_int32), C.POINTER(C.c_double)], C.c_int),
     "rt_scene_update_vertices": ([_VP, _VP, C.c_int32, C.c_int32, C.POINTER(C.c_int32)], C.c_int),
     "rt_scene_update_vertices_device": ([_VP, _VP, C.c_int32, C.c_int32, C.POINTER(C.c_int32)], C.c_int),
     "rt_get_material": ([_VP, C.c_int32, C.POINTER(RtMaterial)], C.c_int),

@@ -148,8 +148,9 @@ class Scene:
     @classmethod
     def create(cls, vertices, triangles, tri_mat, materials: Sequence[dict], device: int = 0,
                builder: str = "sah") -> "Scene":
-        """rt_scene_create_ex. builder 'sah' (the host's binned-SAH build, the default) or 'lbvh' (a
-        Morton-order radix tree; on a device scene built by HIP kernels with no host build)."""
+        """rt_scene_create_ex. builder 'sah' (the host's binned-SAH build, the default), 'lbvh' (a
+        Morton-order radix tree; on a device scene built by HIP kernels with no host build) or 'cluster'
+        (the same leaf order, merged by the surface area of the union box; built the same way)."""
         v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
         t = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
         m = np.ascontiguousarray(tri_mat, np.uint32).reshape(-1)
@@ -167,7 +168,7 @@ class Scene:
         return cls(h, device)
 
     def set_builder(self, name: str) -> None:
-        """rt_scene_set_builder: the builder of the scene's later builds ('sah' or 'lbvh'); rebuilds nothing."""
+        """rt_scene_set_builder: the builder of the scene's later builds ('sah', 'lbvh' or 'cluster'); rebuilds nothing."""
         check(lib().rt_scene_set_builder(self._h, _builder_id(name)))
 
     @property
@@ -176,6 +177,16 @@ class Scene:
         sel, built = C.c_int32(), C.c_int32()
         check(lib().rt_scene_get_builder(self._h, C.byref(sel), C.byref(built)))
         return _capi.BUILDERS[sel.value], _capi.BUILDERS[built.value]
+
+    def build_info(self) -> dict:
+        """rt_scene_build_info: how the current trees were built (built_with, the clustering iterations,
+        the reason of the last fallback from 'cluster', its radius / tail threshold / iteration budget) and
+        the binary tree's cost (child half-areas over the root's), for any builder."""
+        info = (C.c_int32 * _capi.BUILD_INFO_FIELDS)()
+        cost = C.c_double()
+        check(lib().rt_scene_build_info(self._h, info, C.byref(cost)))
+        return dict(built_with=_capi.BUILDERS[info[0]], iterations=info[1], fallback=_capi.FALLBACK_REASONS[info[2]],
+                    radius=info[3], tail=info[4], max_iterations=info[5], cost=cost.value)
 
     def close(self) -> None:
         if self._h:
@@ -221,7 +232,7 @@ class Scene:
         is a float32 (n, 3) array, or a CUDA torch tensor of that shape on the scene's device, which goes
         through rt_scene_update_vertices_device with no host copy. mode 'auto' refits the BVH and rebuilds
         it only if some triangle changed class; 'rebuild' always rebuilds. Returns 'refit', 'rebuilt' (the
-        host SAH build) or 'rebuilt_lbvh' (the Morton-order builder, see set_builder);
+        host SAH build), 'rebuilt_lbvh' (the Morton-order builder, see set_builder) or 'rebuilt_cluster';
         either way the scene then behaves bit for bit as one created from the new vertices."""
         m = {"auto": _capi.UPDATE_AUTO, "rebuild": _capi.UPDATE_REBUILD}.get(mode, mode)
         out = C.c_int32(-1)
@@ -237,7 +248,8 @@ class Scene:
             if v.ndim != 2 or v.shape[1] != 3:
                 raise ValueError("update_vertices: a float32 (n, 3) array is required")
             check(lib().rt_scene_update_vertices(self._h, _ptr(v), len(v), int(m), C.byref(out)))
-        return {_capi.UPDATED_REFIT: "refit", _capi.UPDATED_REBUILT_LBVH: "rebuilt_lbvh"}.get(out.value, "rebuilt")
+        return {_capi.UPDATED_REFIT: "refit", _capi.UPDATED_REBUILT_LBVH: "rebuilt_lbvh",
+                _capi.UPDATED_REBUILT_CLUSTER: "rebuilt_cluster"}.get(out.value, "rebuilt")
 
     def texcoords(self) -> tuple[np.ndarray, np.ndarray]:
         """rt_scene_texcoords (a scene loaded with texcoords=True): (texcoords[n, 3] float32 with z = 0,

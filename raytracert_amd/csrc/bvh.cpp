@@ -45,6 +45,7 @@
 
 #include "rt_internal.h"
 #include "lbvh_shared.h"
+#include "cluster_shared.h"
 
 namespace rt {
 namespace {
@@ -707,7 +708,12 @@ int lbvh_depth_limit() {
     return std::min(std::max(limit, 1), kMaxBvhDepth);
 }
 
-int build_lbvh(const HostScene &s, const std::vector<TriRec> &recs, HostBvh &out) {
+namespace {
+// Steps 1-3 of both device builders: classes and padded boxes, keys, the stable sort. Fills out.always,
+// out.n_never, out.leaf_tris (the Morton-sorted order), the sorted codes and each leaf slot's box.
+// RT_OK, or kLbvhFallback when the leaf index field cannot hold the slots.
+int lbvh_sorted_slots(const HostScene &s, const std::vector<TriRec> &recs, HostBvh &out, std::vector<uint32_t> &codes,
+                      std::vector<Box> &slot) {
     out = HostBvh();
     const size_t nt = recs.size();
     out.scene_m1 = scene_m1_of(s.verts.data(), s.verts.size() / 3);
@@ -724,7 +730,6 @@ int build_lbvh(const HostScene &s, const std::vector<TriRec> &recs, HostBvh &out
     }
     const int32_t np = static_cast<int32_t>(tree.size());
     if (tree.size() >= (size_t(1) << kBvhCountShift)) return kLbvhFallback;   // leaf first-index field
-    const int limit = lbvh_depth_limit();
     auto bits = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
     auto unbits = [](uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; };
     // keys: centroid of the padded box, 10 bits per axis over the centroid bounds
@@ -748,33 +753,74 @@ int build_lbvh(const HostScene &s, const std::vector<TriRec> &recs, HostBvh &out
     std::vector<int32_t> perm(np);
     std::iota(perm.begin(), perm.end(), 0);
     std::stable_sort(perm.begin(), perm.end(), [&](int32_t a, int32_t b) { return code0[a] < code0[b]; });
-    std::vector<uint32_t> codes(np);
-    std::vector<Box> slot(np);
+    codes.resize(np);
+    slot.resize(np);
     out.leaf_tris.resize(np);
     for (int32_t j = 0; j < np; ++j) { codes[j] = code0[perm[j]]; slot[j] = box[perm[j]]; out.leaf_tris[j] = tree[perm[j]]; }
-    auto ref_leaf = [](int32_t first, int32_t count) {
-        return static_cast<int32_t>(kBvhLeafBit | (static_cast<uint32_t>(count) << kBvhCountShift) | static_cast<uint32_t>(first));
-    };
-    if (np <= kMaxLeaf) {   // empty tree, or the whole tree is one leaf wrapped in a root (as build_bvh)
-        BvhNode root{};
-        for (int k = 0; k < 3; ++k) { root.lo0[k] = root.lo1[k] = FLT_MAX; root.hi0[k] = root.hi1[k] = -FLT_MAX; }
-        root.c0 = root.c1 = kBvhEmpty;
-        Bvh4F g = make_node4f(nullptr, nullptr, 0);
-        out.depth = 1;
-        if (np > 0) {
-            Box b;
-            for (int32_t j = 0; j < np; ++j) b.grow(slot[j]);
-            root.c0 = ref_leaf(0, np);
-            for (int k = 0; k < 3; ++k) { root.lo0[k] = b.lo[k]; root.hi0[k] = b.hi[k]; }
-            g = make_node4f(&b, &root.c0, 1);
-            out.depth = 2;
-        }
-        if (out.depth > limit) return kLbvhFallback;
-        out.nodes.push_back(root);
-        out.nodes4f.push_back(g);
-        out.depth4 = 1;
-        return nodes4_from_nodes4f(out) == RT_OK ? RT_OK : kLbvhFallback;
+    return RT_OK;
+}
+
+int32_t ref_leaf(int32_t first, int32_t count) {
+    return static_cast<int32_t>(kBvhLeafBit | (static_cast<uint32_t>(count) << kBvhCountShift) | static_cast<uint32_t>(first));
+}
+
+// np <= kMaxLeaf: the empty tree, or the whole tree as one leaf wrapped in a root (as build_bvh).
+int lbvh_small_tree(HostBvh &out, const std::vector<Box> &slot, int limit) {
+    const int32_t np = static_cast<int32_t>(slot.size());
+    BvhNode root{};
+    for (int k = 0; k < 3; ++k) { root.lo0[k] = root.lo1[k] = FLT_MAX; root.hi0[k] = root.hi1[k] = -FLT_MAX; }
+    root.c0 = root.c1 = kBvhEmpty;
+    Bvh4F g = make_node4f(nullptr, nullptr, 0);
+    out.depth = 1;
+    if (np > 0) {
+        Box b;
+        for (int32_t j = 0; j < np; ++j) b.grow(slot[j]);
+        root.c0 = ref_leaf(0, np);
+        for (int k = 0; k < 3; ++k) { root.lo0[k] = b.lo[k]; root.hi0[k] = b.hi[k]; }
+        g = make_node4f(&b, &root.c0, 1);
+        out.depth = 2;
     }
+    if (out.depth > limit) return kLbvhFallback;
+    out.nodes.push_back(root);
+    out.nodes4f.push_back(g);
+    out.depth4 = 1;
+    return nodes4_from_nodes4f(out) == RT_OK ? RT_OK : kLbvhFallback;
+}
+
+// The four-wide tree of a finished binary tree: binary node a is four-wide node four_of[a] (the nodes at
+// even depth; -1 otherwise); children are the grandchildren, or a child that is a leaf.
+int four_wide_from_binary(HostBvh &out, const std::vector<int32_t> &four_of, int32_t n4) {
+    const int32_t n2 = static_cast<int32_t>(out.nodes.size());
+    out.nodes4f.assign(n4, make_node4f(nullptr, nullptr, 0));
+    for (int32_t a = 0; a < n2; ++a) {
+        if (four_of[a] < 0) continue;
+        Bvh4F &g = out.nodes4f[four_of[a]];
+        int nc = 0;
+        auto put = [&](int32_t ref, const float *lo, const float *hi) {
+            g.child[nc] = (static_cast<uint32_t>(ref) & kBvhLeafBit) ? ref : four_of[ref];
+            for (int k = 0; k < 3; ++k) { g.lo[k][nc] = lo[k]; g.hi[k][nc] = hi[k]; }
+            ++nc;
+        };
+        const BvhNode &n = out.nodes[a];
+        for (int side = 0; side < 2; ++side) {
+            const int32_t ref = side ? n.c1 : n.c0;
+            if (static_cast<uint32_t>(ref) & kBvhLeafBit) { put(ref, side ? n.lo1 : n.lo0, side ? n.hi1 : n.hi0); continue; }
+            const BvhNode &m = out.nodes[ref];
+            put(m.c0, m.lo0, m.hi0);
+            put(m.c1, m.lo1, m.hi1);
+        }
+    }
+    return nodes4_from_nodes4f(out) == RT_OK ? RT_OK : kLbvhFallback;
+}
+}  // namespace
+
+int build_lbvh(const HostScene &s, const std::vector<TriRec> &recs, HostBvh &out) {
+    std::vector<uint32_t> codes;
+    std::vector<Box> slot;
+    if (lbvh_sorted_slots(s, recs, out, codes, slot) != RT_OK) return kLbvhFallback;
+    const int32_t np = static_cast<int32_t>(slot.size());
+    const int limit = lbvh_depth_limit();
+    if (np <= kMaxLeaf) return lbvh_small_tree(out, slot, limit);
     // topology: one radix-tree node per i in [0, np - 1); nodes over more than kMaxLeaf codes are emitted
     const int32_t ni = np - 1;
     std::vector<LbvhRange> rg(ni);
@@ -809,30 +855,120 @@ int build_lbvh(const HostScene &s, const std::vector<TriRec> &recs, HostBvh &out
     }
     // boxes bottom-up: each child box the exact union of what lies below it (the refit's statement)
     Refitter{slot, out}.run2(0);
-    // four-wide: the emitted nodes at even depth; children are the grandchildren, or a child that is a leaf
+    // four-wide: the emitted nodes at even depth
     std::vector<int32_t> four_of(n2, -1);
     for (int32_t i = 0; i < ni; ++i)
         if (id4[i] >= 0) four_of[id2[i]] = id4[i];
-    out.nodes4f.assign(n4, make_node4f(nullptr, nullptr, 0));
-    for (int32_t a = 0; a < n2; ++a) {
-        if (four_of[a] < 0) continue;
-        Bvh4F &g = out.nodes4f[four_of[a]];
-        int nc = 0;
-        auto put = [&](int32_t ref, const float *lo, const float *hi) {
-            g.child[nc] = (static_cast<uint32_t>(ref) & kBvhLeafBit) ? ref : four_of[ref];
-            for (int k = 0; k < 3; ++k) { g.lo[k][nc] = lo[k]; g.hi[k][nc] = hi[k]; }
-            ++nc;
-        };
-        const BvhNode &n = out.nodes[a];
-        for (int side = 0; side < 2; ++side) {
-            const int32_t ref = side ? n.c1 : n.c0;
-            if (static_cast<uint32_t>(ref) & kBvhLeafBit) { put(ref, side ? n.lo1 : n.lo0, side ? n.hi1 : n.hi0); continue; }
-            const BvhNode &m = out.nodes[ref];
-            put(m.c0, m.lo0, m.hi0);
-            put(m.c1, m.lo1, m.hi1);
-        }
+    return four_wide_from_binary(out, four_of, n4);
+}
+
+// ---- the agglomerative builder (RT_BUILD_CLUSTER; DESIGN.md "GPU BVH build: RT_BUILD_CLUSTER") -----
+// The host statement of what the k_cluster_* kernels build, array for array. Steps 1-3 are the Morton
+// builder's (same classes, boxes, keys and sort, so the same leaf order); the radix tree is replaced by
+// clustering in that order (cluster_shared.h): every iteration each cluster finds its nearest neighbour
+// by the half-area of the union box within kClusterRadius positions, mutual pairs merge, the array is
+// compacted. Nodes are numbered in reverse creation order (the root, made last, is node 0; parents
+// precede children); boxes, four-wide collapse and refit state are the Morton builder's.
+
+int build_cluster(const HostScene &s, const std::vector<TriRec> &recs, HostBvh &out, int32_t *iterations, int32_t *reason) {
+    std::vector<uint32_t> codes;
+    std::vector<Box> slot;
+    int32_t it_dummy, why_dummy;
+    int32_t &iters = iterations ? *iterations : it_dummy, &why = reason ? *reason : why_dummy;
+    iters = 0;
+    why = RT_FALLBACK_NONE;
+    if (lbvh_sorted_slots(s, recs, out, codes, slot) != RT_OK) { why = RT_FALLBACK_LEAF_INDEX; return kLbvhFallback; }
+    const int32_t np = static_cast<int32_t>(slot.size());
+    const int limit = lbvh_depth_limit();
+    if (np <= kMaxLeaf) {
+        const int rc = lbvh_small_tree(out, slot, limit);
+        if (rc != RT_OK) why = out.depth > limit ? RT_FALLBACK_DEPTH : RT_FALLBACK_QUANTISE;
+        return rc;
     }
-    return nodes4_from_nodes4f(out) == RT_OK ? RT_OK : kLbvhFallback;
+    // the clusters, ping-pong as the kernels keep them
+    std::vector<uint32_t> ref(np), ref2(np);
+    std::vector<ClusterBox> cb(np), cb2(np);
+    std::vector<int32_t> nn(np);
+    for (int32_t j = 0; j < np; ++j) {
+        ref[j] = static_cast<uint32_t>(ref_leaf(j, 1));
+        for (int k = 0; k < 3; ++k) { cb[j].lo[k] = slot[j].lo[k]; cb[j].hi[k] = slot[j].hi[k]; }
+    }
+    std::vector<std::array<uint32_t, 2>> made;   // child refs of each node, by creation index
+    made.reserve(np);
+    int32_t c = np;
+    for (; c > 1 && iters < kClusterMaxIters; ++iters) {
+        const ClusterBox *boxes = cb.data();
+        for (int32_t i = 0; i < c; ++i) nn[i] = cluster_nearest(i, c, [boxes](int32_t j) -> const ClusterBox & { return boxes[j]; });
+        int32_t w = 0;
+        for (int32_t i = 0; i < c; ++i) {
+            const int32_t j = nn[i];
+            const int role = cluster_role(i, j, j >= 0 ? nn[j] : -1);
+            if (role == 2) continue;
+            if (role == 0) {
+                ref2[w] = ref[i];
+                cb2[w] = cb[i];
+            } else {
+                uint32_t m;
+                if (!cluster_leaf_pair(ref[i], ref[j], &m)) {
+                    m = static_cast<uint32_t>(made.size());
+                    made.push_back({ref[i], ref[j]});
+                }
+                ref2[w] = m;
+                cb2[w] = cluster_union(cb[i], cb[j]);
+            }
+            ++w;
+        }
+        ref.swap(ref2);
+        cb.swap(cb2);
+        c = w;
+    }
+    if (c > 1) { why = RT_FALLBACK_BUDGET; return kLbvhFallback; }
+    // numbering: id = n2 - 1 - creation index; depth from the parents (a parent's id is the smaller one)
+    const int32_t n2 = static_cast<int32_t>(made.size());
+    out.nodes.assign(n2, BvhNode{});
+    std::vector<int32_t> depth(n2, 0), four_of(n2, -1);
+    int32_t n4 = 0, max_depth = 0, max_even = 0;
+    for (int32_t id = 0; id < n2; ++id) {
+        const std::array<uint32_t, 2> &m = made[n2 - 1 - id];
+        int32_t ch[2];
+        for (int side = 0; side < 2; ++side) {
+            ch[side] = (m[side] & kBvhLeafBit) ? static_cast<int32_t>(m[side]) : n2 - 1 - static_cast<int32_t>(m[side]);
+            if (!(m[side] & kBvhLeafBit)) depth[ch[side]] = depth[id] + 1;
+        }
+        out.nodes[id].c0 = ch[0];
+        out.nodes[id].c1 = ch[1];
+        max_depth = std::max(max_depth, depth[id]);
+        if ((depth[id] & 1) == 0) { four_of[id] = n4++; max_even = std::max(max_even, depth[id]); }
+    }
+    out.depth = max_depth + 2;   // the deepest node's children are leaves
+    out.depth4 = max_even / 2 + 1;
+    if (out.depth > limit) { why = RT_FALLBACK_DEPTH; return kLbvhFallback; }
+    // boxes bottom-up: each child box the exact union of what lies below it (the refit's statement)
+    Refitter{slot, out}.run2(0);
+    if (four_wide_from_binary(out, four_of, n4) != RT_OK) { why = RT_FALLBACK_QUANTISE; return kLbvhFallback; }
+    return RT_OK;
+}
+
+// rt_scene_build_info's cost of the binary tree: the sum over inner nodes, in node order and in binary64,
+// of the half-areas of both child boxes, over the half-area of the union of the root's child boxes.
+double bvh_cost(const HostBvh &h) {
+    auto half = [](const float *lo, const float *hi) {
+        const double dx = double(hi[0]) - double(lo[0]), dy = double(hi[1]) - double(lo[1]), dz = double(hi[2]) - double(lo[2]);
+        return (dx * dy + dy * dz) + dz * dx;
+    };
+    if (h.nodes.empty()) return 0.0;
+    double sum = 0;
+    for (const BvhNode &n : h.nodes) {
+        if (n.c0 != kBvhEmpty) sum += half(n.lo0, n.hi0);
+        if (n.c1 != kBvhEmpty) sum += half(n.lo1, n.hi1);
+    }
+    const BvhNode &r = h.nodes[0];
+    Box u;
+    if (r.c0 != kBvhEmpty) { u.grow(r.lo0); u.grow(r.hi0); }
+    if (r.c1 != kBvhEmpty) { u.grow(r.lo1); u.grow(r.hi1); }
+    if (u.empty()) return 0.0;
+    const double root = half(u.lo, u.hi);
+    return root > 0 ? sum / root : 0.0;
 }
 
 namespace {

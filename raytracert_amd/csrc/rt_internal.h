@@ -170,6 +170,12 @@ int nodes4_from_nodes4f(HostBvh &h);
 constexpr int kLbvhFallback = 2;
 int lbvh_depth_limit();   // kMaxBvhDepth, lowered by RTAMD_LBVH_MAX_DEPTH (tests), read at each build
 int build_lbvh(const HostScene &s, const std::vector<TriRec> &recs, HostBvh &out);
+// The agglomerative builder (RT_BUILD_CLUSTER), the host statement of the k_cluster_* kernels: RT_OK, or
+// kLbvhFallback with *reason (RT_FALLBACK_*); the caller then builds with build_lbvh. *iterations: the
+// clustering iterations run.
+int build_cluster(const HostScene &s, const std::vector<TriRec> &recs, HostBvh &out, int32_t *iterations, int32_t *reason);
+// rt_scene_build_info's *cost of a host tree
+double bvh_cost(const HostBvh &h);
 float bvh4_decode(float origin, int ex, uint32_t q);
 uint64_t bvh_digest(const HostBvh &h);
 int validate_bvh(const HostScene &s, const std::vector<TriRec> &recs, const HostBvh &h, std::string &err);

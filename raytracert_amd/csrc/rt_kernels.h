@@ -8,6 +8,7 @@
 
 #include "fastdiv.h"
 #include "rt_internal.h"
+#include "cluster_shared.h"
 
 namespace rt {
 
@@ -250,6 +251,12 @@ struct LbvhStatus {
     uint32_t cnt2[kLbvhHeights], cnt4[kLbvhHeights];   // nodes per height (four-wide: per height group)
     uint32_t off2[kLbvhHeights + 1], off4[kLbvhHeights + 1];
     uint32_t cur2[kLbvhHeights], cur4[kLbvhHeights];
+    // RT_BUILD_CLUSTER: the cluster count and the nodes made so far, before iteration t in entry t & 1 (an
+    // iteration reads one entry and writes the other); the iterations that merged something
+    uint32_t cl_count[2], cl_made[2], cl_iters;
+    uint32_t cl_live;   // which of the ping-pong cluster arrays the last iteration that ran wrote (what the tail reads)
+    // ... and after k_cluster_tail: the final cluster count (1: finished), the nodes made, the iterations run
+    uint32_t cl_final_count, cl_final_made, cl_final_iters;
 };
 struct LbvhArgs {
     const float *xyz;          // 3 per vertex (nv)
@@ -265,6 +272,12 @@ struct LbvhArgs {
     uint32_t *bcnt, *bbase;         // 2 per block of 256 radix-tree nodes
     uint32_t *bpart;                // k_lbvh_classify's per-block centroid bounds (6 per block of 256 of max(nt, nv))
     unsigned long long *bm1;        // ... and m1 bits (1 per block)
+    // RT_BUILD_CLUSTER (cluster_shared.h): the clusters' refs and boxes, ping-pong; each one's nearest
+    // neighbour; the child refs of each node by creation index
+    uint32_t *cl_ref[2];
+    ClusterBox *cl_box[2];
+    int32_t *cl_nn;
+    uint2 *cl_pair;
     int32_t sort_blocks;
     // outputs (nt entries each; slot_box 2 per slot)
     BvhNode *nodes;
@@ -278,7 +291,17 @@ struct LbvhArgs {
 };
 // The whole build on `stream`, no host round trip: classes, keys, stable radix sort, radix tree, numbering,
 // `sweeps` bottom-up box sweeps (a root they do not reach is too deep), four-wide collapse, refit tables.
-hipError_t launch_lbvh_build(const LbvhArgs &a, int sweeps, hipStream_t stream);
+// builder RT_BUILD_CLUSTER: the radix tree and its numbering are replaced by kClusterMaxIters clustering
+// iterations of four launches each (lanes exit on the device-side cluster count, at kClusterTail clusters or
+// fewer), one launch of one workgroup that runs what is left of the budget in LDS, and the numbering of
+// the nodes they made; everything before and after is the same launches.
+hipError_t launch_lbvh_build(const LbvhArgs &a, int sweeps, hipStream_t stream, int32_t builder = RT_BUILD_LBVH);
+// The agglomerative build in pieces, for a host that reads the cluster count back between groups of
+// iterations instead of queueing the whole budget: everything up to the first clusters; iterations
+// [t0, t0 + n); the tail (reading entry t_end & 1 of the counts) and everything after it.
+hipError_t launch_cluster_front(const LbvhArgs &a, hipStream_t stream);
+hipError_t launch_cluster_iterations(const LbvhArgs &a, int t0, int n, hipStream_t stream);
+hipError_t launch_cluster_back(const LbvhArgs &a, int t_end, int sweeps, hipStream_t stream);
 // Un-permute gathered tile shards ([nranks][slots][th][tw][3], tile g of the frames x T tiles in
 // rank g % nranks, slot g / nranks) into frames x height x width x 3 bytes; with slot0 / nslots, a
 // gather chunk holding slots [slot0, slot0 + nslots) of every rank ([nranks][nslots][th][tw][3]).

@@ -3405,6 +3405,324 @@ __global__ __launch_bounds__(kBlock) void k_lbvh_tables(const LbvhArgs a, const 
     }
 }
 
+// ---- GPU BVH build: agglomerative clustering (RT_BUILD_CLUSTER; host statement: bvh.cpp build_cluster) ----
+// The rule of the Morton builder's kernels holds here too: no workgroup waits on another, and what one
+// launch writes only later launches read (the clusters, their counts and the nodes made are ping-pong:
+// iteration t reads entry t & 1 and writes the other). Launches are sized by nt; lanes exit on the
+// device-side cluster count: at kClusterTail clusters or fewer the iterations still queued do nothing and
+// one workgroup finishes in LDS (k_cluster_tail). The host may queue the budget blind or read the count back
+// between groups of iterations (launch_cluster_*); the kernels are the same. Every index read from memory is range-checked and sets
+// status->error.
+
+// One lane per leaf slot: cluster j is leaf slot j alone, with its padded box.
+__global__ __launch_bounds__(kBlock) void k_cluster_init(const LbvhArgs a) {
+    const int64_t j = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    const uint32_t np = a.status->np;
+    if (j == 0) {
+        a.status->cl_count[0] = np > RT_BVH_MAX_LEAF ? np : 0u;   // (k_lbvh_levels makes the trees of one leaf)
+        a.status->cl_made[0] = 0u;
+    }
+    if (j >= np || j >= a.nt || np <= RT_BVH_MAX_LEAF) return;
+    const float4 l = a.slot_box[2 * j], h = a.slot_box[2 * j + 1];
+    a.cl_ref[0][j] = kBvhLeafBit | (1u << kBvhCountShift) | static_cast<uint32_t>(j);
+    a.cl_box[0][j] = ClusterBox{{l.x, l.y, l.z}, {h.x, h.y, h.z}};
+}
+
+// One lane per cluster: its nearest neighbour (cluster_nearest). The block's boxes and a halo of
+// kClusterRadius on each side are staged in LDS.
+__global__ __launch_bounds__(kBlock) void k_cluster_nn(const LbvhArgs a, int t) {
+    __shared__ ClusterBox stage[kBlock + 2 * kClusterRadius];
+    const int64_t c64 = a.status->cl_count[t & 1];
+    const int64_t base = static_cast<int64_t>(blockIdx.x) * kBlock;
+    if (c64 <= kClusterTail || base >= c64 || c64 > a.nt) return;   // (block-uniform)
+    const int32_t c = static_cast<int32_t>(c64), first = static_cast<int32_t>(base) - kClusterRadius;
+    const ClusterBox *__restrict__ in = a.cl_box[t & 1];
+    for (int s = threadIdx.x; s < kBlock + 2 * kClusterRadius; s += kBlock) {
+        const int32_t pos = first + s;
+        if (pos >= 0 && pos < c) stage[s] = in[pos];
+    }
+    __syncthreads();
+    const int32_t i = static_cast<int32_t>(base) + static_cast<int32_t>(threadIdx.x);
+    if (i >= c) return;
+    const ClusterBox *sp = stage;
+    a.cl_nn[i] = cluster_nearest(i, c, [sp, first](int32_t j) -> const ClusterBox & { return sp[j - first]; });
+}
+
+// What cluster i does in iteration t (cluster_role), and whether its merge makes a node; `other`: the
+// position it merges with.
+__device__ __forceinline__ int cluster_decide(const LbvhArgs &a, int t, int32_t i, int32_t c, int32_t &other, uint32_t &merged,
+                                              bool &node) {
+    node = false;
+    merged = 0;
+    other = a.cl_nn[i];
+    if (other >= c || other == i) { other = -1; a.status->error = 1; }
+    const int role = cluster_role(i, other, other >= 0 ? a.cl_nn[other] : -1);
+    if (role == 1) node = !cluster_leaf_pair(a.cl_ref[t & 1][i], a.cl_ref[t & 1][other], &merged);
+    return role;
+}
+
+// Per block of 256 clusters: how many survive the iteration and how many nodes their merges make.
+__global__ __launch_bounds__(kBlock) void k_cluster_mark(const LbvhArgs a, int t) {
+    __shared__ uint32_t cs[kBlock / 64], cm[kBlock / 64];
+    const int64_t c64 = a.status->cl_count[t & 1];
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (c64 <= kClusterTail || static_cast<int64_t>(blockIdx.x) * kBlock >= c64 || c64 > a.nt) return;   // (block-uniform)
+    bool lives = false, node = false;
+    if (i < c64) {
+        int32_t other;
+        uint32_t merged;
+        lives = cluster_decide(a, t, static_cast<int32_t>(i), static_cast<int32_t>(c64), other, merged, node) != 2;
+    }
+    const unsigned long long bs = __ballot(lives), bm = __ballot(node);
+    if ((threadIdx.x & 63) == 0) {
+        cs[threadIdx.x >> 6] = static_cast<uint32_t>(__popcll(bs));
+        cm[threadIdx.x >> 6] = static_cast<uint32_t>(__popcll(bm));
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t s = 0, m = 0;
+        for (int w = 0; w < kBlock / 64; ++w) { s += cs[w]; m += cm[w]; }
+        a.bcnt[2 * static_cast<int64_t>(blockIdx.x)] = s;
+        a.bcnt[2 * static_cast<int64_t>(blockIdx.x) + 1] = m;
+    }
+}
+
+// Exclusive scan of the per-block count pairs by one workgroup (k_lbvh_idscan's scan); the totals are the
+// next iteration's cluster count and the nodes made so far. Once the count is the tail's, both are copied.
+__global__ __launch_bounds__(kScanBlock) void k_cluster_scan(const LbvhArgs a, int t) {
+    __shared__ uint32_t s2[kScanBlock], s4[kScanBlock];
+    const int64_t c64 = a.status->cl_count[t & 1];
+    const uint32_t made = a.status->cl_made[t & 1];
+    if (c64 <= kClusterTail || c64 > a.nt) {   // (block-uniform)
+        if (threadIdx.x == 0) { a.status->cl_count[(t + 1) & 1] = static_cast<uint32_t>(c64); a.status->cl_made[(t + 1) & 1] = made; }
+        return;
+    }
+    const int64_t nb = (c64 + kBlock - 1) / kBlock;
+    const int64_t per = (nb + kScanBlock - 1) / kScanBlock;
+    const int64_t b = per * threadIdx.x, e = b + per < nb ? b + per : nb;
+    uint32_t t2 = 0, t4 = 0;
+    for (int64_t i = b; i < e; ++i) { t2 += a.bcnt[2 * i]; t4 += a.bcnt[2 * i + 1]; }
+    s2[threadIdx.x] = t2;
+    s4[threadIdx.x] = t4;
+    __syncthreads();
+    for (int o = 1; o < kScanBlock; o <<= 1) {
+        const bool on = static_cast<int>(threadIdx.x) >= o;
+        const uint32_t x = on ? s2[threadIdx.x - o] : 0u, y = on ? s4[threadIdx.x - o] : 0u;
+        __syncthreads();
+        s2[threadIdx.x] += x;
+        s4[threadIdx.x] += y;
+        __syncthreads();
+    }
+    uint32_t a2 = s2[threadIdx.x] - t2, a4 = s4[threadIdx.x] - t4;
+    for (int64_t i = b; i < e; ++i) {
+        a.bbase[2 * i] = a2;
+        a.bbase[2 * i + 1] = made + a4;
+        a2 += a.bcnt[2 * i];
+        a4 += a.bcnt[2 * i + 1];
+    }
+    if (threadIdx.x == kScanBlock - 1) {
+        a.status->cl_count[(t + 1) & 1] = s2[threadIdx.x];
+        a.status->cl_made[(t + 1) & 1] = made + s4[threadIdx.x];
+        a.status->cl_iters = static_cast<uint32_t>(t) + 1u;
+        a.status->cl_live = static_cast<uint32_t>((t + 1) & 1);
+    }
+}
+
+// The merges and the compaction: a surviving cluster moves to its new position (the prefix sum of the
+// survivors), a merged one with the union box and either a two-triangle leaf ref or a new node's creation
+// index (the prefix sum of the nodes made, after those of the earlier iterations); the node's two child
+// refs are recorded under that index.
+__global__ __launch_bounds__(kBlock) void k_cluster_apply(const LbvhArgs a, int t) {
+    __shared__ uint32_t cs[kBlock / 64], cm[kBlock / 64];
+    const int64_t c64 = a.status->cl_count[t & 1];
+    const int64_t i64 = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (c64 <= kClusterTail || static_cast<int64_t>(blockIdx.x) * kBlock >= c64 || c64 > a.nt) return;   // (block-uniform)
+    const int32_t i = static_cast<int32_t>(i64), c = static_cast<int32_t>(c64);
+    int role = 2, other = -1;
+    uint32_t merged = 0;
+    bool node = false;
+    if (i64 < c64) role = cluster_decide(a, t, i, c, other, merged, node);
+    const bool lives = role != 2;
+    const unsigned long long bs = __ballot(lives), bm = __ballot(node);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) { cs[wave] = static_cast<uint32_t>(__popcll(bs)); cm[wave] = static_cast<uint32_t>(__popcll(bm)); }
+    __syncthreads();
+    if (!lives) return;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    uint32_t w = a.bbase[2 * static_cast<int64_t>(blockIdx.x)] + static_cast<uint32_t>(__popcll(bs & below));
+    uint32_t k = a.bbase[2 * static_cast<int64_t>(blockIdx.x) + 1] + static_cast<uint32_t>(__popcll(bm & below));
+    for (int v = 0; v < wave; ++v) { w += cs[v]; k += cm[v]; }
+    if (w >= static_cast<uint32_t>(c) || (node && k >= static_cast<uint32_t>(a.nt))) { a.status->error = 1; return; }
+    const uint32_t *__restrict__ rin = a.cl_ref[t & 1];
+    const ClusterBox *__restrict__ bin = a.cl_box[t & 1];
+    uint32_t ref = rin[i];
+    ClusterBox box = bin[i];
+    if (role == 1) {
+        const uint32_t rj = rin[other];
+        box = cluster_union(box, bin[other]);
+        if (node) { a.cl_pair[k] = make_uint2(ref, rj); ref = k; }
+        else ref = merged;
+    }
+    a.cl_ref[(t + 1) & 1][w] = ref;
+    a.cl_box[(t + 1) & 1][w] = box;
+}
+
+// The last kClusterTail clusters or fewer: one workgroup, one cluster per lane, runs what is left of the
+// iteration budget with the clusters in LDS (the same cluster_nearest / cluster_role / cluster_leaf_pair, the
+// same prefix sums, so the same tree); workgroup barriers only, and a loop with a fixed bound. Reads entry
+// `fin` of the counts, writes the final ones.
+__global__ __launch_bounds__(kScanBlock) void k_cluster_tail(const LbvhArgs a, int fin) {
+    static_assert(kClusterTail == kScanBlock, "one lane per cluster, and the LDS arrays are indexed by every lane");
+    __shared__ ClusterBox sbox[kClusterTail];
+    __shared__ uint32_t sref[kClusterTail];
+    __shared__ int32_t snn[kClusterTail];
+    __shared__ uint32_t s2[kScanBlock], s4[kScanBlock];
+    const int32_t i = static_cast<int32_t>(threadIdx.x);
+    int32_t c = static_cast<int32_t>(a.status->cl_count[fin]);
+    uint32_t made = a.status->cl_made[fin], iters = a.status->cl_iters;
+    if (c > kClusterTail || c > a.nt) {   // (block-uniform; the budget ended before the tail's size: the host falls back)
+        if (i == 0) { a.status->cl_final_count = static_cast<uint32_t>(c); a.status->cl_final_made = made; a.status->cl_final_iters = iters; }
+        return;
+    }
+    const uint32_t live = a.status->cl_live & 1u;   // (the iterations queued after the hand-over copy the counts, not the clusters)
+    if (i < c) { sref[i] = a.cl_ref[live][i]; sbox[i] = a.cl_box[live][i]; }
+    for (int it = 0; it < kClusterMaxIters; ++it) {
+        __syncthreads();
+        if (c <= 1 || iters >= static_cast<uint32_t>(kClusterMaxIters)) break;   // (block-uniform)
+        const ClusterBox *sp = sbox;
+        const int32_t j = i < c ? cluster_nearest(i, c, [sp](int32_t p) -> const ClusterBox & { return sp[p]; }) : -1;
+        snn[i] = j;
+        __syncthreads();
+        const int role = i < c ? cluster_role(i, j, j >= 0 ? snn[j] : -1) : 2;
+        uint32_t merged = 0;
+        const bool node = role == 1 && !cluster_leaf_pair(sref[i], sref[j], &merged);
+        const uint32_t lives = role != 2 ? 1u : 0u, makes = node ? 1u : 0u;
+        s2[i] = lives;
+        s4[i] = makes;
+        __syncthreads();
+        for (int o = 1; o < kScanBlock; o <<= 1) {
+            const bool on = i >= o;
+            const uint32_t x = on ? s2[i - o] : 0u, y = on ? s4[i - o] : 0u;
+            __syncthreads();
+            s2[i] += x;
+            s4[i] += y;
+            __syncthreads();
+        }
+        const uint32_t w = s2[i] - lives, k = made + s4[i] - makes;
+        const uint32_t left = s2[kScanBlock - 1], more = s4[kScanBlock - 1];
+        uint32_t ref = 0;
+        ClusterBox box{};
+        if (lives) {
+            ref = sref[i];
+            box = sbox[i];
+            if (role == 1) {
+                const uint32_t rj = sref[j];
+                box = cluster_union(box, sbox[j]);
+                if (!node) ref = merged;
+                else if (k < static_cast<uint32_t>(a.nt)) { a.cl_pair[k] = make_uint2(ref, rj); ref = k; }
+                else a.status->error = 1;
+            }
+        }
+        __syncthreads();
+        if (lives) { sref[w] = ref; sbox[w] = box; }
+        c = static_cast<int32_t>(left);
+        made += more;
+        ++iters;
+    }
+    if (i == 0) { a.status->cl_final_count = static_cast<uint32_t>(c); a.status->cl_final_made = made; a.status->cl_final_iters = iters; }
+}
+
+// After the tail: one lane per node made, numbered in reverse creation
+// order (id = n2 - 1 - creation index: the root, made last, is node 0 and parents precede children). Its
+// child refs (boxes come from the sweeps) and its children's parent links. A child made later than its
+// parent would be a cycle: it is an error, so the walks and sweeps below are bounded.
+__global__ __launch_bounds__(kBlock) void k_cluster_nodes(const LbvhArgs a) {
+    const int64_t id = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    const uint32_t n2 = a.status->cl_final_made;
+    if (a.status->cl_final_count != 1u || n2 > static_cast<uint32_t>(a.nt)) return;   // (not finished: the host falls back)
+    if (id == 0) a.status->n2 = n2;
+    if (id >= n2) return;
+    const uint32_t k = n2 - 1u - static_cast<uint32_t>(id);
+    const uint2 m = a.cl_pair[k];
+    int32_t ref[2];
+    for (int side = 0; side < 2; ++side) {
+        const uint32_t r = side ? m.y : m.x;
+        if (r & kBvhLeafBit) { ref[side] = static_cast<int32_t>(r); continue; }
+        if (r >= k) { ref[side] = kBvhEmpty; a.status->error = 1; continue; }
+        ref[side] = static_cast<int32_t>(n2 - 1u - r);
+        a.parent[ref[side]] = static_cast<int32_t>(id);
+    }
+    float4 *g = reinterpret_cast<float4 *>(a.nodes + id);
+    g[0] = make_float4(0, 0, 0, 0); g[1] = g[0]; g[2] = g[0];
+    g[3] = make_float4(as_float(ref[0]), as_float(ref[1]), 0.0f, 0.0f);
+}
+
+// One lane per node: its depth (a bounded walk up the parents the launch before wrote) and whether it is a
+// four-wide node (even depth); per block of 256 the two counts for k_lbvh_idscan (every node is a binary
+// node). k_cluster_ids repeats the walk and takes the ids from the scan.
+__device__ __forceinline__ bool cluster_even_depth(const LbvhArgs &a, int64_t id, uint32_t n2, int32_t &d) {
+    d = 0;
+    for (int32_t p = a.parent[id]; p >= 0 && d <= kMaxBvhDepth; p = a.parent[p]) {
+        if (static_cast<uint32_t>(p) >= n2) { a.status->error = 1; break; }
+        ++d;
+    }
+    return (d & 1) == 0;
+}
+
+__global__ __launch_bounds__(kBlock) void k_cluster_flags(const LbvhArgs a) {
+    __shared__ uint32_t c2[kBlock / 64], c4[kBlock / 64];
+    const int64_t id = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    const uint32_t n2 = a.status->n2;
+    bool e2 = false, e4 = false;
+    uint32_t md = 0, me = 0;
+    if (id < n2 && id < a.nt) {
+        int32_t d;
+        e2 = true;
+        e4 = cluster_even_depth(a, id, n2, d);
+        md = static_cast<uint32_t>(d);
+        if (e4) me = md;
+    }
+    const unsigned long long b2 = __ballot(e2), b4 = __ballot(e4);
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t x = __shfl_xor(md, o), y = __shfl_xor(me, o);
+        md = x > md ? x : md;
+        me = y > me ? y : me;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        c2[threadIdx.x >> 6] = static_cast<uint32_t>(__popcll(b2));
+        c4[threadIdx.x >> 6] = static_cast<uint32_t>(__popcll(b4));
+        if (md) atomicMax(&a.status->max_depth, md);
+        if (me) atomicMax(&a.status->max_even, me);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t s2 = 0, s4 = 0;
+        for (int w = 0; w < kBlock / 64; ++w) { s2 += c2[w]; s4 += c4[w]; }
+        a.bcnt[2 * static_cast<int64_t>(blockIdx.x)] = s2;
+        a.bcnt[2 * static_cast<int64_t>(blockIdx.x) + 1] = s4;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_cluster_ids(const LbvhArgs a) {
+    __shared__ uint32_t c4[kBlock / 64];
+    const int64_t id = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    const uint32_t n2 = a.status->n2;
+    const bool in = id < n2 && id < a.nt;
+    bool e4 = false;
+    if (in) {
+        int32_t d;
+        e4 = cluster_even_depth(a, id, n2, d);
+    }
+    const unsigned long long b4 = __ballot(e4);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) c4[wave] = static_cast<uint32_t>(__popcll(b4));
+    __syncthreads();
+    if (!in) return;
+    uint32_t r4 = a.bbase[2 * static_cast<int64_t>(blockIdx.x) + 1] + static_cast<uint32_t>(__popcll(b4 & ((1ull << lane) - 1ull)));
+    for (int w = 0; w < wave; ++w) r4 += c4[w];
+    a.four_of[id] = e4 ? static_cast<int32_t>(r4) : -1;
+}
+
 // rayIntersectTriangle (raytracing.cpp:99-154) for n independent (ray, triangle) pairs, every
 // step in the reference's order; unlike intersectMesh's use of it there is no distance compare, so
 // a hit whose point is NaN or infinite is still reported, as the reference returns true for it.
@@ -3924,10 +4242,18 @@ void launch_refit_tris(const RefitArgs &a, hipStream_t stream) {
     hipLaunchKernelGGL(k_refit_tris, dim3(grid_for(n)), dim3(kBlock), 0, stream, a);
 }
 
-hipError_t launch_lbvh_build(const LbvhArgs &a, int sweeps, hipStream_t st) {
+namespace {
+struct LbvhGrids { unsigned tri, nt, sort; };
+LbvhGrids lbvh_grids(const LbvhArgs &a) {
     const int64_t nt = a.nt, cap = std::max<int64_t>(nt, 1);
-    const unsigned g_tri = grid_for(std::max<int64_t>(std::max<int64_t>(nt, a.nv), 1)), g_nt = grid_for(cap);
-    const unsigned g_sort = static_cast<unsigned>(a.sort_blocks);
+    return LbvhGrids{grid_for(std::max<int64_t>(std::max<int64_t>(nt, a.nv), 1)), grid_for(cap), static_cast<unsigned>(a.sort_blocks)};
+}
+
+// Steps 1-3 of both builders: classes and boxes, keys, the stable sort (the sorted keys and triangles end in key_a / val_a).
+hipError_t lbvh_front(const LbvhArgs &a, hipStream_t st) {
+    const int64_t cap = std::max<int64_t>(a.nt, 1);
+    const LbvhGrids g = lbvh_grids(a);
+    const unsigned g_tri = g.tri, g_nt = g.nt, g_sort = g.sort;
     hipError_t e = hipMemsetAsync(a.status, 0, sizeof(LbvhStatus), st);
     if (e == hipSuccess) e = hipMemsetAsync(a.parent, 0xFF, sizeof(int32_t) * cap, st);
     if (e == hipSuccess) e = hipMemsetAsync(a.h_a, 0xFF, sizeof(int32_t) * cap, st);
@@ -3951,12 +4277,12 @@ hipError_t launch_lbvh_build(const LbvhArgs &a, int sweeps, hipStream_t st) {
         hipLaunchKernelGGL(k_lbvh_scatter, dim3(g_sort), dim3(kBlock), 0, st, ki, vi, ko, vo, &a.status->np, 0, static_cast<int>(cap),
                            8 * pass, a.table_scan, a.sort_blocks);
     }
-    hipLaunchKernelGGL(k_lbvh_topo, dim3(g_nt), dim3(kBlock), 0, st, a);
-    hipLaunchKernelGGL(k_lbvh_gather, dim3(g_nt), dim3(kBlock), 0, st, a);
-    hipLaunchKernelGGL(k_lbvh_flags, dim3(g_nt), dim3(kBlock), 0, st, a);
-    hipLaunchKernelGGL(k_lbvh_idscan, dim3(1), dim3(kScanBlock), 0, st, a, static_cast<int64_t>(g_nt));
-    hipLaunchKernelGGL(k_lbvh_ids, dim3(g_nt), dim3(kBlock), 0, st, a);
-    hipLaunchKernelGGL(k_lbvh_nodes2, dim3(g_nt), dim3(kBlock), 0, st, a);
+    return hipSuccess;
+}
+
+// Boxes bottom-up, the four-wide collapse and the refit's tables, from the binary nodes' child refs and four_of.
+void lbvh_back(const LbvhArgs &a, int sweeps, hipStream_t st) {
+    const unsigned g_nt = lbvh_grids(a).nt;
     const int32_t *h_fin = a.h_a;
     for (int k = 0; k < sweeps; ++k) {   // one launch per height: the kernel boundary carries the boxes
         const int32_t *h_in = (k & 1) ? a.h_b : a.h_a;
@@ -3967,6 +4293,56 @@ hipError_t launch_lbvh_build(const LbvhArgs &a, int sweeps, hipStream_t st) {
     hipLaunchKernelGGL(k_lbvh_levels, dim3(1), dim3(64), 0, st, a, h_fin);
     hipLaunchKernelGGL(k_lbvh_emit4, dim3(g_nt), dim3(kBlock), 0, st, a);
     hipLaunchKernelGGL(k_lbvh_tables, dim3(g_nt), dim3(kBlock), 0, st, a, h_fin);
+}
+}  // namespace
+
+hipError_t launch_cluster_front(const LbvhArgs &a, hipStream_t st) {
+    const hipError_t e = lbvh_front(a, st);
+    if (e != hipSuccess) return e;
+    const unsigned g_nt = lbvh_grids(a).nt;
+    hipLaunchKernelGGL(k_lbvh_gather, dim3(g_nt), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(k_cluster_init, dim3(g_nt), dim3(kBlock), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_iterations(const LbvhArgs &a, int t0, int n, hipStream_t st) {
+    const unsigned g_nt = lbvh_grids(a).nt;
+    for (int t = t0; t < t0 + n; ++t) {
+        hipLaunchKernelGGL(k_cluster_nn, dim3(g_nt), dim3(kBlock), 0, st, a, t);
+        hipLaunchKernelGGL(k_cluster_mark, dim3(g_nt), dim3(kBlock), 0, st, a, t);
+        hipLaunchKernelGGL(k_cluster_scan, dim3(1), dim3(kScanBlock), 0, st, a, t);
+        hipLaunchKernelGGL(k_cluster_apply, dim3(g_nt), dim3(kBlock), 0, st, a, t);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_back(const LbvhArgs &a, int t_end, int sweeps, hipStream_t st) {
+    const unsigned g_nt = lbvh_grids(a).nt;
+    hipLaunchKernelGGL(k_cluster_tail, dim3(1), dim3(kScanBlock), 0, st, a, t_end & 1);
+    hipLaunchKernelGGL(k_cluster_nodes, dim3(g_nt), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(k_cluster_flags, dim3(g_nt), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(k_lbvh_idscan, dim3(1), dim3(kScanBlock), 0, st, a, static_cast<int64_t>(g_nt));
+    hipLaunchKernelGGL(k_cluster_ids, dim3(g_nt), dim3(kBlock), 0, st, a);
+    lbvh_back(a, sweeps, st);
+    return hipGetLastError();
+}
+
+hipError_t launch_lbvh_build(const LbvhArgs &a, int sweeps, hipStream_t st, int32_t builder) {
+    if (builder == RT_BUILD_CLUSTER) {   // the whole budget, blind: an iteration's launches exit on the device-side cluster count
+        hipError_t e = launch_cluster_front(a, st);
+        if (e == hipSuccess) e = launch_cluster_iterations(a, 0, kClusterMaxIters, st);
+        return e == hipSuccess ? launch_cluster_back(a, kClusterMaxIters, sweeps, st) : e;
+    }
+    const hipError_t e = lbvh_front(a, st);
+    if (e != hipSuccess) return e;
+    const unsigned g_nt = lbvh_grids(a).nt;
+    hipLaunchKernelGGL(k_lbvh_topo, dim3(g_nt), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(k_lbvh_gather, dim3(g_nt), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(k_lbvh_flags, dim3(g_nt), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(k_lbvh_idscan, dim3(1), dim3(kScanBlock), 0, st, a, static_cast<int64_t>(g_nt));
+    hipLaunchKernelGGL(k_lbvh_ids, dim3(g_nt), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(k_lbvh_nodes2, dim3(g_nt), dim3(kBlock), 0, st, a);
+    lbvh_back(a, sweeps, st);
     return hipGetLastError();
 }
 
