@@ -14,6 +14,9 @@
  *   rt_ray_intersect_triangle  rayIntersectTriangle (batched pairs)  raytracing.cpp:99-154
  *   rt_intersect_mesh     intersectMesh (batched)           raytracing.cpp:161-192
  *   rt_trace_rays         Vec3Df performRayTracing(o, d)    raytracing.h:33, raytracing.cpp:410-416
+ *   rt_intersect_mesh_device  intersectMesh, rays and results in device memory   raytracing.cpp:161-192
+ *   rt_occluded_device    isShadow's verdict for given rays, in device memory  raytracing.cpp:249-258
+ *   rt_trace_rays_device  performRayTracing, rays and colours in device memory raytracing.cpp:410-416
  *   rt_debug_trace        debug key 'd' (shoot + trace)     raytracing.cpp:493-510
  *                         (batched; also trace(o,d,lvl) at lvl 0, raytracing.h:30)
  *   rt_render_tile        the 'r'-key frame loop            main.cpp:340-411 (loop :355-395,
@@ -231,6 +234,48 @@ int rt_intersect_mesh(rt_scene *scene, const float *origins, const float *dests,
  * counts (may be NULL) receives {primary, secondary, shadow} intersectMesh-equivalent queries. */
 int rt_trace_rays(rt_scene *scene, const rt_params *params, const float *origins, const float *dests,
                   int32_t n, float *rgb_out, uint64_t counts[3]);
+
+/* Device-resident ray queries (extensions: the reference's rays live in host Vec3Df's). The three entries
+ * below answer n rays that are already in DEVICE memory on the scene's device and write their results to
+ * DEVICE memory, on the caller's stream: no host copy and, unless stated, no host synchronisation. Ray i is
+ * the half-line from origin[i] through dest[i], exactly as the host entries read it. ray_stride says how the
+ * two ray arrays are laid out: RT_RAYS_PACKED, a contiguous float32 (n,3) array; RT_RAYS_PADDED, (n,4) with
+ * w ignored and the array 16-byte aligned. Results are always packed. Outputs must not overlap inputs
+ * (nor d_count): the kernels read the rays while they write results.
+ * stream is the caller's hipStream_t (NULL = the null stream), semantics as rt_render_tiles_device: the work
+ * starts after what is already queued on the stream and later work queued on it sees the results.
+ * A later rt_scene_update_vertices[_device], tree rebuild or rt_scene_destroy waits for the queries still in
+ * flight before it writes or frees what they read, so a query queued before an update answers for the old
+ * vertices and one queued after it for the new.
+ * d_count (rt_intersect_mesh_device, rt_occluded_device; may be NULL): a device int32 that the kernel reads
+ * when it runs, in stream order, never on the host; the live ray count is min(max(*d_count, 0), n), n is then
+ * the capacity the launch is sized for, and output elements at or past the live count are not written. A
+ * producer kernel on the same stream can thus decide the count without a host synchronisation.
+ * Errors (scene untouched, nothing enqueued): RT_E_NODEV on a host-only scene (checked first); RT_E_ARG for a
+ * NULL scene, n < 0, a ray_stride other than 3 or 4, a NULL array with n > 0, a pointer that is not 4-byte
+ * aligned (16-byte for the ray arrays at RT_RAYS_PADDED). n == 0 is RT_OK with nothing enqueued. */
+#define RT_RAYS_PACKED 3   /* x,y,z per ray, 12 bytes apart: a contiguous float32 (n,3) array */
+#define RT_RAYS_PADDED 4   /* x,y,z,w per ray, 16 bytes apart, w ignored; 16-byte aligned */
+/* intersectMesh (raytracing.cpp:161-192) for rays in device memory: d_index_out[i] (n x int32) = closest
+ * triangle or -1, d_point_out[3*i..] (3n packed floats) = hit point or (0,0,0), bit for bit what
+ * rt_intersect_mesh returns for the same rays. Returns after enqueueing; uses no render workspace. */
+int rt_intersect_mesh_device(rt_scene *scene, const void *d_origins, const void *d_dests, int32_t ray_stride,
+                             int32_t n, const void *d_count, void *d_index_out, void *d_point_out, void *stream);
+/* isShadow's verdict (raytracing.cpp:249-258) for caller-given rays: d_blocked_out[i] (n x uint8) = 1 when
+ * the ray's CLOSEST hit exists and its material is not transparent (transparent: RT_HAS_TR and Tr < 1,
+ * raytracing.cpp:254), else 0. As in the reference a transparent closest hit does not block whatever lies
+ * behind it. No 0.1 offset is added (raytracing.cpp:246 is the frame path's own): the caller supplies the
+ * origin it wants. Returns after enqueueing; uses no render workspace. */
+int rt_occluded_device(rt_scene *scene, const void *d_origins, const void *d_dests, int32_t ray_stride,
+                       int32_t n, const void *d_count, void *d_blocked_out, void *stream);
+/* performRayTracing (raytracing.cpp:410-416) for rays in device memory: d_rgb_out[3*i..] (3n packed floats),
+ * bit for bit rt_trace_rays' rgb_out. counts as in rt_trace_rays; non-NULL synchronises the stream. Uses
+ * render pipeline 0's workspace (ordered against the frames that use it): returns after enqueueing when
+ * counts == NULL and that workspace is already large enough (rt_scene_reserve, or an earlier call of this
+ * size). n * max(n_lights, 1) <= 2^30 and the params rules as rt_trace_rays. No d_count: the chain's queues
+ * are sized on the host. */
+int rt_trace_rays_device(rt_scene *scene, const rt_params *params, const void *d_origins, const void *d_dests,
+                         int32_t ray_stride, int32_t n, void *d_rgb_out, void *stream, uint64_t counts[3]);
 
 /* Single-ray debug trace (the reference's key 'd', raytracing.cpp:493-510, which shoots one ray,
  * keeps (origin, intersection) for drawing and prints the traced colour): one record per trace()

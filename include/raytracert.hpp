@@ -164,6 +164,23 @@ class RayTracer {
         return out;
     }
 
+    // Extensions: the same queries for rays that are already in device memory, results to device memory, on
+    // the caller's hipStream_t with no host copy (rt_intersect_mesh_device, rt_occluded_device,
+    // rt_trace_rays_device; ray_stride RT_RAYS_PACKED or RT_RAYS_PADDED, d_count may be null).
+    void intersect_mesh_device(const void *d_origins, const void *d_dests, int32_t ray_stride, int32_t n, const void *d_count,
+                               void *d_index_out, void *d_point_out, void *stream) {
+        check(rt_intersect_mesh_device(scene_, d_origins, d_dests, ray_stride, n, d_count, d_index_out, d_point_out, stream));
+    }
+    void occluded_device(const void *d_origins, const void *d_dests, int32_t ray_stride, int32_t n, const void *d_count,
+                         void *d_blocked_out, void *stream) {
+        check(rt_occluded_device(scene_, d_origins, d_dests, ray_stride, n, d_count, d_blocked_out, stream));
+    }
+    void perform_ray_tracing_device(const void *d_origins, const void *d_dests, int32_t ray_stride, int32_t n, void *d_rgb_out,
+                                    void *stream, uint64_t counts[3] = nullptr) {
+        rt_params p = params();
+        check(rt_trace_rays_device(scene_, &p, d_origins, d_dests, ray_stride, n, d_rgb_out, stream, counts));
+    }
+
     // the debug key 'd' (raytracing.cpp:493-510): every trace() of the ray's chain, and its colour
     std::vector<rt_debug_bounce> debugTrace(const Vec3Df &origin, const Vec3Df &dest, Vec3Df *color = nullptr) {
         std::vector<rt_debug_bounce> b(static_cast<size_t>(max_lvl) * 2 + 2);

@@ -289,6 +289,104 @@ class Scene:
         check(lib().rt_trace_rays(self._h, C.byref(p), _ptr(o), _ptr(d), n, _ptr(rgb), _ptr(counts)))
         return rgb, counts
 
+    # -- device-resident queries (rays and results are torch CUDA tensors; stream-ordered, no host sync) ----
+    def _device_rays(self, name: str, host_method: str, origins, dests):
+        """Checks before anything touches a device: (n, ray_stride) of two CUDA float32 ray tensors."""
+        import torch
+        for what, t in (("origins", origins), ("dests", dests)):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{name}: {what} must be a CUDA torch tensor (host arrays go through {host_method})")
+            if t.dtype != torch.float32:
+                raise ValueError(f"{name}: {what} must be float32, not {t.dtype}")
+            if t.dim() != 2 or t.shape[1] not in (_capi.RAYS_PACKED, _capi.RAYS_PADDED):
+                raise ValueError(f"{name}: {what} must have shape (n, 3) or (n, 4), not {tuple(t.shape)}")
+            if not t.is_contiguous():
+                raise ValueError(f"{name}: {what} must be contiguous")
+            if not t.is_cuda:
+                raise ValueError(f"{name}: {what} is a CPU tensor (host arrays go through {host_method})")
+            if t.device.index != self.device:
+                raise ValueError(f"{name}: {what} is on {t.device}, the scene on device {self.device}")
+        if origins.shape != dests.shape:
+            raise ValueError(f"{name}: origins {tuple(origins.shape)} and dests {tuple(dests.shape)} differ in shape")
+        return int(origins.shape[0]), int(origins.shape[1])
+
+    def _device_count(self, name: str, count):
+        import torch
+        if count is None:
+            return None
+        if (not isinstance(count, torch.Tensor) or not count.is_cuda or count.dtype != torch.int32 or count.numel() != 1
+                or count.device.index != self.device):
+            raise ValueError(f"{name}: count must be a CUDA int32 tensor of one element on the scene's device")
+        return C.c_void_p(count.data_ptr())
+
+    def _device_out(self, name: str, out, n: int, dtype, tail: tuple, fill, counted: bool):
+        """The result tensor: `out` checked (it may hold more than n rows; only the first n are the
+        result), or a new one, filled first when a device count may leave entries unwritten."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            shape = (n,) + tail
+            return torch.full(shape, fill, dtype=dtype, device=dev) if counted else torch.empty(shape, dtype=dtype, device=dev)
+        if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.device.index != self.device or out.dtype != dtype
+                or not out.is_contiguous() or out.dim() != 1 + len(tail) or tuple(out.shape[1:]) != tail or out.shape[0] < n):
+            raise ValueError(f"{name}: out must be a contiguous CUDA {dtype} tensor of shape (>= {n},) + {tail} on the scene's device")
+        return out
+
+    def _stream_ptr(self, stream):
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        s = getattr(stream, "cuda_stream", stream)
+        return C.c_void_p(int(s)) if s else None
+
+    def intersect_mesh_device(self, origins, dests, count=None, out=None, stream=None):
+        """rt_intersect_mesh_device: intersectMesh for rays born on the GPU. origins / dests are contiguous
+        CUDA float32 tensors on the scene's device, (n, 3) or (n, 4) (w ignored); count an optional CUDA int32
+        tensor of one element, read by the kernel (live rays = clamp(count, 0, n); the rest is not written);
+        out an optional (index, point) pair to write into (rows past n are left alone). Returns (index[n]
+        int32, point[n, 3] float32) CUDA tensors, rt_intersect_mesh's values bit for bit. Stream-ordered on
+        `stream` (a torch stream or its cuda_stream; default: the current stream): nothing is synchronised.
+        With a stream other than the one the tensors were made on, keeping them alive and ordered is the
+        caller's business (Tensor.record_stream)."""
+        import torch
+        name = "intersect_mesh_device"
+        n, stride = self._device_rays(name, "intersect_mesh", origins, dests)
+        cnt = self._device_count(name, count)
+        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
+            raise ValueError(f"{name}: out must be an (index, point) pair")
+        idx = self._device_out(name, None if out is None else out[0], n, torch.int32, (), -1, count is not None)
+        pts = self._device_out(name, None if out is None else out[1], n, torch.float32, (3,), 0.0, count is not None)
+        check(lib().rt_intersect_mesh_device(self._h, C.c_void_p(origins.data_ptr()), C.c_void_p(dests.data_ptr()), stride, n,
+                                             cnt, C.c_void_p(idx.data_ptr()), C.c_void_p(pts.data_ptr()), self._stream_ptr(stream)))
+        return idx[:n], pts[:n]
+
+    def occluded_device(self, origins, dests, count=None, out=None, stream=None):
+        """rt_occluded_device: isShadow's verdict for the given rays (arguments as intersect_mesh_device).
+        Returns blocked[n] uint8: 1 when the ray's closest hit exists and its material is not transparent,
+        else 0. No offset is added to the origins."""
+        import torch
+        name = "occluded_device"
+        n, stride = self._device_rays(name, "intersect_mesh", origins, dests)
+        cnt = self._device_count(name, count)
+        blocked = self._device_out(name, out, n, torch.uint8, (), 0, count is not None)
+        check(lib().rt_occluded_device(self._h, C.c_void_p(origins.data_ptr()), C.c_void_p(dests.data_ptr()), stride, n, cnt,
+                                       C.c_void_p(blocked.data_ptr()), self._stream_ptr(stream)))
+        return blocked[:n]
+
+    def perform_ray_tracing_device(self, params: RenderParams, origins, dests, out=None, stream=None, want_counts: bool = False):
+        """rt_trace_rays_device: performRayTracing for rays born on the GPU (arguments as
+        intersect_mesh_device, without count). Returns rgb[n, 3] float32 (unclamped, perform_ray_tracing's
+        bits), or (rgb, counts[3]) with want_counts, which synchronises the stream."""
+        import torch
+        name = "perform_ray_tracing_device"
+        n, stride = self._device_rays(name, "perform_ray_tracing", origins, dests)
+        rgb = self._device_out(name, out, n, torch.float32, (3,), 0.0, False)
+        counts = np.zeros(3, np.uint64) if want_counts else None
+        p = params.to_c() if isinstance(params, RenderParams) else params
+        check(lib().rt_trace_rays_device(self._h, C.byref(p), C.c_void_p(origins.data_ptr()), C.c_void_p(dests.data_ptr()), stride,
+                                         n, C.c_void_p(rgb.data_ptr()), self._stream_ptr(stream), _ptr(counts)))
+        return (rgb[:n], counts) if want_counts else rgb[:n]
+
     def debug_trace(self, params: RenderParams, origin, dest, max_bounces: int = 256):
         """The debug key 'd' (raytracing.cpp:493-510) for one ray: (bounces, rgb). Each bounce is
         a dict (origin, dest, hit, triangle, level, shadowed, lit) for one trace() call, in

@@ -203,6 +203,17 @@ void launch_estimate(const DevScene &s, const ShadeParams &p, const FrameGeom &g
                      uint32_t *score, hipStream_t stream);
 void launch_intersect_only(const DevScene &s, const float4 *org, const float4 *dst, int32_t n,
                            int32_t *idx, float4 *I, hipStream_t stream);
+// Device-resident ray queries (rt_intersect_mesh_device / rt_occluded_device): n rays at org/dst in the
+// caller's layout (ray_stride 3: packed x,y,z; 4: x,y,z,w 16-B aligned), launch_intersect_only's launch
+// shape. d_count (may be null): a device int32 read by the kernel; rays at or past min(max(*d_count, 0), n)
+// are neither read nor written. !occluded: idx[n] and point[3 n] (packed), launch_intersect_only's values.
+// occluded: blocked[n] bytes, k_bvh_shadow_hit's verdict (any-hit walk when the scene has no transparent
+// material in use, else closest hit and its material's test). The other outputs may be null.
+void launch_query_rays(const DevScene &s, bool occluded, const void *org, const void *dst, int32_t ray_stride, int32_t n,
+                       const int32_t *d_count, int32_t *idx, float *point, uint8_t *blocked, hipStream_t stream);
+// launch_gen_rays from the caller's device arrays in either layout (rt_trace_rays_device)
+void launch_gen_rays_device(const void *org, const void *dst, int32_t ray_stride, int32_t n, const DevWork &w,
+                            hipStream_t stream);
 // calculateNormals on the device (face normal per triangle into normals[i].xyz)
 void launch_face_normals(const float *xyz, const uint32_t *tri_v, int32_t nt, float4 *normals, hipStream_t stream);
 // True when this build's test_triangle reads RN(1/D) from the records' D slot (RT_TRI_RCP): the

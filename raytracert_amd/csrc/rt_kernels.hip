@@ -1479,6 +1479,94 @@ __global__ __launch_bounds__(kBlock) void k_intersect_only(const TriRec *__restr
 }
 
 // ---------------------------------------------------------------------------------------------
+// Device-resident ray queries (rt_intersect_mesh_device, rt_occluded_device): rays read straight from
+// the caller's arrays (kStride 3: x,y,z 12 bytes apart, a wave's 64 rays 768 contiguous bytes; kStride 4:
+// one float4 per ray, w ignored), results written straight to the caller's (packed points, indices,
+// verdict bytes). d_count (may be null) is read when the kernel runs: the live count min(max(*d_count, 0), n)
+// is the same for every lane (a scalar load), and nothing at or past it is read or written.
+// kQueryClosest: intersectMesh (raytracing.cpp:161-192), k_bvh_intersect_only's arithmetic.
+// kQueryOccludedClosest: isShadow's verdict (raytracing.cpp:249-258) from the closest hit's material.
+// kQueryOccludedAny: the same verdict when no material in use is transparent (any accepted triangle
+// blocks), by the any-hit walk.
+// ---------------------------------------------------------------------------------------------
+enum : int { kQueryClosest = 0, kQueryOccludedClosest = 1, kQueryOccludedAny = 2 };
+
+template <int kStride>
+__device__ __forceinline__ V3 load_ray_point(const void *__restrict__ a, int j) {
+    if (kStride == 4) {
+        const float4 v = static_cast<const float4 *>(a)[j];
+        return mk(v.x, v.y, v.z);
+    }
+    return static_cast<const V3 *>(a)[j];   // three packed floats
+}
+
+__device__ __forceinline__ int live_rays(const int32_t *__restrict__ d_count, int n) {
+    return d_count ? min(max(*d_count, 0), n) : n;
+}
+
+template <int kMode>
+__device__ __forceinline__ void store_query(const uint32_t *__restrict__ tri_mat, const DevMaterial *__restrict__ mats, int j,
+                                            int bidx, V3 bI, int32_t *__restrict__ idx, float *__restrict__ point,
+                                            uint8_t *__restrict__ blocked) {
+    if (kMode == kQueryClosest) {
+        idx[j] = bidx;
+        reinterpret_cast<V3 *>(point)[j] = bI;
+    } else {
+        uint8_t sh = 0;
+        if (bidx >= 0) sh = mats[tri_mat[bidx]].transparent ? 0 : 1;               // :253-257
+        blocked[j] = sh;
+    }
+}
+
+template <int W, int kMode, int kStride, bool kCount>
+__global__ __launch_bounds__(kBvhBlock) void k_bvh_query_rays(const DevScene sc, const void *__restrict__ org,
+                                                              const void *__restrict__ dst, int n,
+                                                              const int32_t *__restrict__ d_count, int32_t *__restrict__ idx,
+                                                              float *__restrict__ point, uint8_t *__restrict__ blocked) {
+    extern __shared__ int32_t lds_stack[];
+    const LaneStack stack = lane_stack(sc, lds_stack);
+    WorkTally<kCount> wt;
+    drive_queries(live_rays(d_count, n), 0, nullptr, [&](int j, int end) {
+        const bool active = j < end;
+        V3 o = mk(0, 0, 0), dir = mk(0, 0, 0);
+        if (active) {
+            o = load_ray_point<kStride>(org, j);
+            dir = sub(load_ray_point<kStride>(dst, j), o);                          // :111
+        }
+        int bidx = -1;
+        V3 bI = mk(0, 0, 0);
+        wt.begin();
+        bvh_query_w<kMode == kQueryOccludedAny, W>(sc, o, dir, active, bidx, bI, stack, wt.tests, wt.visits);
+        wt.end();
+        if (active) store_query<kMode>(sc.tri_mat, sc.mats, j, bidx, bI, idx, point, blocked);
+    });
+    wt.flush(kMode == kQueryClosest ? sc.work : sc.work ? sc.work + kWorkFields : nullptr);
+}
+
+// The same over every triangle in index order (RT_ACCEL_BRUTE_FORCE, or no tree could be built).
+template <int kMode, int kStride>
+__global__ __launch_bounds__(kBlock) void k_query_rays(const TriRec *__restrict__ tris, int nt, const uint32_t *__restrict__ tri_mat,
+                                                       const DevMaterial *__restrict__ mats, const void *__restrict__ org,
+                                                       const void *__restrict__ dst, int n, const int32_t *__restrict__ d_count,
+                                                       int32_t *__restrict__ idx, float *__restrict__ point,
+                                                       uint8_t *__restrict__ blocked) {
+    const int live = live_rays(d_count, n);
+    const int64_t base = static_cast<int64_t>(blockIdx.x) * kBlock;
+    if (base >= live) return;
+    const bool active = base + threadIdx.x < live;
+    const int j = active ? static_cast<int>(base + threadIdx.x) : 0;
+    V3 o = mk(0, 0, 0), dir = mk(0, 0, 0);
+    if (active) {
+        o = load_ray_point<kStride>(org, j);
+        dir = sub(load_ray_point<kStride>(dst, j), o);
+    }
+    int bidx = -1;
+    V3 bI = mk(0, 0, 0);
+    closest_hit_loop<kMode == kQueryOccludedAny>(tris, nt, o, dir, active, bidx, bI);
+    if (active) store_query<kMode>(tri_mat, mats, j, bidx, bI, idx, point, blocked);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Sample generation: main.cpp:377-386 for every sub-sample of the batch's tiles.
 // ---------------------------------------------------------------------------------------------
 // (Indices are below 2^31: batches are capped at 2^30 samples and tile ids at 2^30, rt_capi.cpp.)
@@ -1597,6 +1685,19 @@ __global__ __launch_bounds__(kBlock) void k_gen_rays(const float4 *__restrict__ 
     if (s >= n) return;
     if (s == 0) w.counters[0] = n;
     const float4 o = org[s], d = dst[s];
+    w.q_org[0][s] = make_float4(o.x, o.y, o.z, as_float(s));
+    w.q_dst[0][s] = make_float4(d.x, d.y, d.z, as_float(0));
+    w.depth[s] = 0;
+}
+
+// The same from the caller's device arrays (rt_trace_rays_device; kStride as load_ray_point).
+template <int kStride>
+__global__ __launch_bounds__(kBlock) void k_gen_rays_device(const void *__restrict__ org, const void *__restrict__ dst,
+                                                            int32_t n, DevWork w) {
+    const int s = blockIdx.x * kBlock + threadIdx.x;
+    if (s >= n) return;
+    if (s == 0) w.counters[0] = n;
+    const V3 o = load_ray_point<kStride>(org, s), d = load_ray_point<kStride>(dst, s);
     w.q_org[0][s] = make_float4(o.x, o.y, o.z, as_float(s));
     w.q_dst[0][s] = make_float4(d.x, d.y, d.z, as_float(0));
     w.depth[s] = 0;
@@ -4224,6 +4325,46 @@ void launch_intersect_only(const DevScene &s0, const float4 *org, const float4 *
         return;
     }
     hipLaunchKernelGGL(k_intersect_only, dim3(grid_for(n)), dim3(kBlock), 0, stream, s0.tris, s0.nt, org, dst, n, idx, I);
+}
+
+namespace {
+template <int kMode, int kStride>
+void launch_query_mode(const DevScene &s0, const void *org, const void *dst, int32_t n, const int32_t *d_count, int32_t *idx,
+                       float *point, uint8_t *blocked, hipStream_t stream) {
+    if (s0.use_bvh) {   // launch_intersect_only's shape
+        const int W = s0.bvh_width == 4 ? 4 : 2;
+        const DevScene s = for_width(s0, W);
+        auto k = W == 4 ? (s.work ? k_bvh_query_rays<4, kMode, kStride, true> : k_bvh_query_rays<4, kMode, kStride, false>)
+                        : (s.work ? k_bvh_query_rays<2, kMode, kStride, true> : k_bvh_query_rays<2, kMode, kStride, false>);
+        hipLaunchKernelGGL(k, dim3(grid_bvh(n, s.bvh_grid)), dim3(kBvhBlock), bvh_lds(s), stream, s, org, dst, n, d_count, idx,
+                           point, blocked);
+        return;
+    }
+    hipLaunchKernelGGL((k_query_rays<kMode, kStride>), dim3(grid_for(n)), dim3(kBlock), 0, stream, s0.tris, s0.nt, s0.tri_mat,
+                       s0.mats, org, dst, n, d_count, idx, point, blocked);
+}
+}  // namespace
+
+void launch_query_rays(const DevScene &s, bool occluded, const void *org, const void *dst, int32_t ray_stride, int32_t n,
+                       const int32_t *d_count, int32_t *idx, float *point, uint8_t *blocked, hipStream_t stream) {
+    if (n <= 0) return;
+    const bool wide = ray_stride == 4;
+    if (!occluded) {
+        if (wide) launch_query_mode<kQueryClosest, 4>(s, org, dst, n, d_count, idx, point, blocked, stream);
+        else launch_query_mode<kQueryClosest, 3>(s, org, dst, n, d_count, idx, point, blocked, stream);
+    } else if (s.any_transparent) {   // a transparent closest hit does not block, whatever lies behind it
+        if (wide) launch_query_mode<kQueryOccludedClosest, 4>(s, org, dst, n, d_count, idx, point, blocked, stream);
+        else launch_query_mode<kQueryOccludedClosest, 3>(s, org, dst, n, d_count, idx, point, blocked, stream);
+    } else {
+        if (wide) launch_query_mode<kQueryOccludedAny, 4>(s, org, dst, n, d_count, idx, point, blocked, stream);
+        else launch_query_mode<kQueryOccludedAny, 3>(s, org, dst, n, d_count, idx, point, blocked, stream);
+    }
+}
+
+void launch_gen_rays_device(const void *org, const void *dst, int32_t ray_stride, int32_t n, const DevWork &w, hipStream_t stream) {
+    if (n <= 0) return;
+    if (ray_stride == 4) hipLaunchKernelGGL(k_gen_rays_device<4>, dim3(grid_for(n)), dim3(kBlock), 0, stream, org, dst, n, w);
+    else hipLaunchKernelGGL(k_gen_rays_device<3>, dim3(grid_for(n)), dim3(kBlock), 0, stream, org, dst, n, w);
 }
 
 void launch_normal_table(float4 *normals, float4 *ntab, int32_t nt, hipStream_t stream) {
