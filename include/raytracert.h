@@ -10,6 +10,8 @@
  *   rt_scene_create       Mesh(vertices, triangles) ctor    mesh.h:175 (+ materials, mesh.h:197-200)
  *   rt_scene_destroy      (globals live for the process: main.cpp:17-18,130)
  *   rt_scene_export       read access to MyMesh / normals   raytracing.h:8, raytracing.cpp:33
+ *   rt_scene_set_mesh     (nothing in the reference: the mesh is fixed after init; an extension, as
+ *                         rt_scene_update_vertices: vertices, triangles and their materials replaced)
  *   rt_get_material       Material getMaterial(int)         raytracing.h:27, raytracing.cpp:373-376
  *   rt_ray_intersect_triangle  rayIntersectTriangle (batched pairs)  raytracing.cpp:99-154
  *   rt_intersect_mesh     intersectMesh (batched)           raytracing.cpp:161-192
@@ -183,6 +185,38 @@ int  rt_scene_update_vertices(rt_scene *scene, const float *xyz, int32_t n_verti
  * own stream. RT_E_NODEV on a host-only scene. */
 int  rt_scene_update_vertices_device(rt_scene *scene, const void *d_xyz, int32_t n_vertices, int32_t mode,
                                      int32_t *outcome);
+/* Topology changes (an extension; nothing in the reference, whose mesh is fixed after init): replace the
+ * scene's vertices, triangle indices and triangle materials. The counts may differ from the scene's in
+ * either direction, n_triangles == 0 included. The material table, the chosen builder, the accel mode, the
+ * profiling mode and the tuning knobs stay; texture coordinates are dropped (rt_scene_texcoords then
+ * reports 0 texcoords and a zero tri_t). After a successful return every entry behaves bit for bit as on a
+ * scene made by rt_scene_create_ex from the same arrays, the scene's materials and the scene's builder
+ * (frames, host and device queries, rt_debug_trace, rt_scene_export, rt_get_material, rt_scene_bvh_*, a
+ * later rt_scene_update_vertices). *outcome (may be NULL) reports the builder that made the new trees with
+ * the RT_UPDATED_REBUILT* values, as an update does (RT_MESH_REPLACED names the call's plain success).
+ * The work runs on the scene's stream after every render and device query queued before it and is complete
+ * on return: a query queued before answers for the old mesh, one queued after for the new. Render
+ * workspaces, streams, events, the stack overflow area and the builders' scratch are kept; batch orders
+ * and launch trials are reset to a new scene's; per-triangle and per-vertex device buffers are reallocated
+ * only when a count exceeds their capacity (with a device builder a replacement inside it allocates
+ * nothing). On a host-only scene rt_scene_set_mesh runs creation's host path.
+ * Errors, the scene untouched and still answering for the old mesh: RT_E_ARG for a NULL scene, a negative
+ * count, a NULL array with a non-zero count; RT_E_PARSE "triangle references a missing vertex" /
+ * "triangle references a missing material" (rt_scene_create_ex's checks and texts). */
+#define RT_MESH_REPLACED 0
+int  rt_scene_set_mesh(rt_scene *scene, const float *xyz, int32_t n_vertices, const uint32_t *tri_v,
+                       const uint32_t *tri_mat, int32_t n_triangles, int32_t *outcome);
+/* The same from device memory on the scene's device, complete when the call is made (read on the scene's
+ * own stream). With RT_BUILD_LBVH / RT_BUILD_CLUSTER nothing is copied to the host: the indices are
+ * validated by a kernel whose verdict is read before anything dereferences one, records, normals and
+ * trees are made by the kernels of rt_scene_update_vertices and of the builders, and the host mirror is
+ * read back only when a host consumer asks. d_counts (may be NULL): a device int32[2] {live vertices,
+ * live triangles}, read in stream order (one 8-byte synchronising read) and clamped to [0, n_vertices] /
+ * [0, n_triangles], which are then the arrays' capacities; entries past the live counts are never read and
+ * the scene afterwards has the live counts (rt_scene_info). RT_E_NODEV on a host-only scene (checked
+ * first); RT_E_ARG also for a device pointer that is not 4-byte aligned. */
+int  rt_scene_set_mesh_device(rt_scene *scene, const void *d_xyz, int32_t n_vertices, const void *d_tri_v,
+                              const void *d_tri_mat, int32_t n_triangles, const void *d_counts, int32_t *outcome);
 
 /* ---- tree builder ---------------------------------------------------------------------
  * Which builder makes a scene's trees. Every builder gives the same output bytes (any tree whose boxes

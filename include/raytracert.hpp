@@ -120,6 +120,24 @@ class RayTracer {
                                        rebuild ? RT_UPDATE_REBUILD : RT_UPDATE_AUTO, &outcome));
         return outcome == RT_UPDATED_REFIT;
     }
+    // Extension: MyMesh's vertices, triangles and triangle materials replaced, counts free to change
+    // (rt_scene_set_mesh; triangles = 3 vertex indices each). The materials, builder and settings stay.
+    // Returns the RT_UPDATED_REBUILT* value of the builder that made the new trees.
+    int32_t setMesh(const std::vector<Vec3Df> &vertices, const std::vector<uint32_t> &triangles,
+                    const std::vector<uint32_t> &triangleMaterials) {
+        int32_t outcome = RT_UPDATED_REBUILT;
+        check(rt_scene_set_mesh(scene_, vertices.empty() ? nullptr : vertices[0].p, static_cast<int32_t>(vertices.size()),
+                                triangles.data(), triangleMaterials.data(), static_cast<int32_t>(triangleMaterials.size()), &outcome));
+        return outcome;
+    }
+    // The same from device memory on the scene's device (rt_scene_set_mesh_device): float xyz[3 nv], uint32
+    // tri_v[3 nt], uint32 tri_mat[nt]; d_counts: null, or a device int32[2] of live counts.
+    int32_t setMeshDevice(const void *d_xyz, int32_t n_vertices, const void *d_tri_v, const void *d_tri_mat, int32_t n_triangles,
+                          const void *d_counts = nullptr) {
+        int32_t outcome = RT_UPDATED_REBUILT;
+        check(rt_scene_set_mesh_device(scene_, d_xyz, n_vertices, d_tri_v, d_tri_mat, n_triangles, d_counts, &outcome));
+        return outcome;
+    }
     // The builder of later rebuilds (rt_scene_set_builder): RT_BUILD_SAH (the default), RT_BUILD_LBVH, the
     // Morton-order tree built on the GPU (same results, a far cheaper rebuild, somewhat slower frames), or
     // RT_BUILD_CLUSTER, the agglomerative tree built on the GPU (a little dearer to build, faster frames).

@@ -66,6 +66,7 @@ UPDATE_AUTO, UPDATE_REBUILD = 0, 1      # rt_scene_update_vertices modes
 UPDATED_REFIT, UPDATED_REBUILT = 0, 1   # ... and outcomes
 UPDATED_REBUILT_LBVH = 2                # ... the trees rebuilt by the Morton-order builder
 UPDATED_REBUILT_CLUSTER = 3             # ... by the agglomerative builder
+MESH_REPLACED = 0                       # rt_scene_set_mesh: RT_OK; *outcome is one of the UPDATED_REBUILT* values
 BUILD_SAH, BUILD_LBVH, BUILD_CLUSTER = 0, 1, 2   # rt_scene_set_builder
 BUILDERS = ("sah", "lbvh", "cluster")
 BUILD_INFO_FIELDS = 6
@@ -122,6 +123,8 @@ _SIGNATURES = {
     "rt_scene_build_info": ([_VP, C.POINTER(C.c_int32), C.POINTER(C.c_double)], C.c_int),
     "rt_scene_update_vertices": ([_VP, _VP, C.c_int32, C.c_int32, C.POINTER(C.c_int32)], C.c_int),
     "rt_scene_update_vertices_device": ([_VP, _VP, C.c_int32, C.c_int32, C.POINTER(C.c_int32)], C.c_int),
+    "rt_scene_set_mesh": ([_VP, _VP, C.c_int32, _VP, _VP, C.c_int32, C.POINTER(C.c_int32)], C.c_int),
+    "rt_scene_set_mesh_device": ([_VP, _VP, C.c_int32, _VP, _VP, C.c_int32, _VP, C.POINTER(C.c_int32)], C.c_int),
     "rt_get_material": ([_VP, C.c_int32, C.POINTER(RtMaterial)], C.c_int),
     "rt_ray_intersect_triangle": ([C.c_int32, _VP, _VP, C.c_int32, _VP, _VP], C.c_int),
     "rt_intersect_mesh": ([_VP, _VP, _VP, C.c_int32, _VP, _VP], C.c_int),

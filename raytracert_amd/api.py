@@ -251,6 +251,51 @@ class Scene:
         return {_capi.UPDATED_REFIT: "refit", _capi.UPDATED_REBUILT_LBVH: "rebuilt_lbvh",
                 _capi.UPDATED_REBUILT_CLUSTER: "rebuilt_cluster"}.get(out.value, "rebuilt")
 
+    def set_mesh(self, vertices, triangles, tri_mat, counts=None) -> str:
+        """rt_scene_set_mesh: replace the scene's vertices, triangles and triangle materials (the counts may
+        change; the material table, builder and tuning stay; texture coordinates are dropped). NumPy arrays
+        (float32 (nv, 3), uint32 (nt, 3), uint32 (nt,)) go through the host entry. Contiguous torch CUDA
+        tensors on the scene's device (float32; int32 or uint32 read as 32-bit words) go through
+        rt_scene_set_mesh_device with no host copy; `counts` is then an optional int32 CUDA tensor
+        {live vertices, live triangles}, the tensors' sizes being capacities. Returns the builder that made
+        the new trees as update_vertices does ('rebuilt', 'rebuilt_lbvh' or 'rebuilt_cluster'); the scene then
+        behaves bit for bit as one created from the same arrays."""
+        out = C.c_int32(-1)
+        if any(hasattr(a, "data_ptr") for a in (vertices, triangles, tri_mat)):
+            import torch
+            words = (torch.int32, getattr(torch, "uint32", torch.int32))
+            for what, t, dtypes, tail in (("vertices", vertices, (torch.float32,), (3,)), ("triangles", triangles, words, (3,)),
+                                          ("tri_mat", tri_mat, words, ())):
+                if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != self.device:
+                    raise ValueError(f"set_mesh: {what} must be a CUDA torch tensor on the scene's device {self.device}")
+                if t.dtype not in dtypes or tuple(t.shape[1:]) != tail or t.dim() != 1 + len(tail):
+                    raise ValueError(f"set_mesh: {what} must be {dtypes[0]} of shape (n,{' 3' if tail else ''}), "
+                                     f"not {t.dtype} {tuple(t.shape)}")
+                if not t.is_contiguous():
+                    raise ValueError(f"set_mesh: {what} must be contiguous")
+            if triangles.shape[0] != tri_mat.shape[0]:
+                raise ValueError("set_mesh: triangles and tri_mat differ in length")
+            cnt = None
+            if counts is not None:
+                if (not isinstance(counts, torch.Tensor) or not counts.is_cuda or counts.dtype != torch.int32
+                        or counts.numel() != 2 or not counts.is_contiguous() or counts.device.index != self.device):
+                    raise ValueError("set_mesh: counts must be a CUDA int32 tensor of two elements on the scene's device")
+                cnt = C.c_void_p(counts.data_ptr())
+            torch.cuda.current_stream(vertices.device).synchronize()   # the library reads them on its own stream
+            check(lib().rt_scene_set_mesh_device(self._h, C.c_void_p(vertices.data_ptr()), int(vertices.shape[0]),
+                                                 C.c_void_p(triangles.data_ptr()), C.c_void_p(tri_mat.data_ptr()),
+                                                 int(triangles.shape[0]), cnt, C.byref(out)))
+        else:
+            if counts is not None:
+                raise ValueError("set_mesh: counts goes with CUDA tensors (host arrays carry their own sizes)")
+            v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+            t = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
+            m = np.ascontiguousarray(tri_mat, np.uint32).reshape(-1)
+            if len(t) != len(m):
+                raise ValueError("set_mesh: triangles and tri_mat differ in length")
+            check(lib().rt_scene_set_mesh(self._h, _ptr(v), len(v), _ptr(t), _ptr(m), len(m), C.byref(out)))
+        return {_capi.UPDATED_REBUILT_LBVH: "rebuilt_lbvh", _capi.UPDATED_REBUILT_CLUSTER: "rebuilt_cluster"}.get(out.value, "rebuilt")
+
     def texcoords(self) -> tuple[np.ndarray, np.ndarray]:
         """rt_scene_texcoords (a scene loaded with texcoords=True): (texcoords[n, 3] float32 with z = 0,
         tri_t[nt, 3] uint32), Mesh::texcoords and each Triangle::t."""

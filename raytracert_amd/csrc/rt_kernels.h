@@ -247,6 +247,19 @@ void launch_refit_tris(const RefitArgs &a, hipStream_t stream);
 // One height of a tree: ids[0..n) are its nodes; call in increasing height, one launch each.
 void launch_refit_level4(Bvh4F *nodes, const int32_t *ids, int32_t n, const float4 *slot_box, hipStream_t stream);
 void launch_refit_level2(BvhNode *nodes, const int32_t *ids, int32_t n, const float4 *slot_box, hipStream_t stream);
+// ---- topology changes (rt_scene_set_mesh_device; DESIGN.md "Topology changes") ----
+// The verdict on a caller's device mesh, read back once: references rt_scene_create_ex would reject, and
+// upload_scene's any_transparent of the new mesh (some material in use is transparent).
+struct MeshStatus {
+    uint32_t bad_vertex_refs;      // tri_v entries >= nv
+    uint32_t bad_material_refs;    // tri_mat entries >= nm
+    uint32_t any_transparent;
+    uint32_t pad;
+};
+// Zeroes status and the nm-byte table `used`, then k_mesh_validate (one lane per triangle; reads tri_v and
+// tri_mat only, never a vertex) and k_mesh_transparent (used x mats[].transparent) on `stream`.
+hipError_t launch_mesh_validate(const uint32_t *tri_v, const uint32_t *tri_mat, int32_t nt, int32_t nv, int32_t nm, const DevMaterial *mats,
+                                uint8_t *used, MeshStatus *status, hipStream_t stream);
 // ---- GPU BVH build (RT_BUILD_LBVH; DESIGN.md "GPU BVH build", host statement: bvh.cpp build_lbvh) ----
 constexpr int kLbvhSortItems = 2048;              // keys per workgroup of the radix passes
 constexpr int kLbvhHeights = kMaxBvhDepth + 1;

@@ -2973,6 +2973,42 @@ __global__ __launch_bounds__(kBlock) void k_refit_level2(BvhNode *__restrict__ n
     for (int k = 0; k < 3; ++k) { lo[k] = b.lo[k]; hi[k] = b.hi[k]; }
 }
 
+// ---- topology changes: validation of a caller's device mesh (rt_scene_set_mesh_device) ---------------
+// rt_scene_create_ex's two checks, one lane per triangle. Reads tri_v and tri_mat only: no vertex is loaded
+// here, and nothing else loads one through these indices until the host has read a clean verdict. Each wave
+// adds its counts of bad vertex references and bad material references to the status with one atomic each
+// (none when the wave found nothing). A valid material is marked in use in the nm-byte table: plain byte
+// stores of 1, whichever lane comes last stores the same value.
+__global__ __launch_bounds__(kBlock) void k_mesh_validate(const uint32_t *__restrict__ tri_v, const uint32_t *__restrict__ tri_mat,
+                                                          int32_t nt, uint32_t nv, uint32_t nm, uint8_t *__restrict__ used,
+                                                          MeshStatus *__restrict__ status) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    uint32_t bad_v = 0, bad_m = 0;
+    if (i < nt) {
+        const uint32_t ia = tri_v[3 * i], ib = tri_v[3 * i + 1], ic = tri_v[3 * i + 2];
+        bad_v = (ia >= nv ? 1u : 0u) + (ib >= nv ? 1u : 0u) + (ic >= nv ? 1u : 0u);
+        const uint32_t m = tri_mat[i];
+        if (m >= nm) bad_m = 1;
+        else used[m] = 1;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        bad_v += __shfl_xor(bad_v, o);
+        bad_m += __shfl_xor(bad_m, o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (bad_v) atomicAdd(&status->bad_vertex_refs, bad_v);
+        if (bad_m) atomicAdd(&status->bad_material_refs, bad_m);
+    }
+}
+
+// The table k_mesh_validate's launch marked (a later launch: the kernel boundary carries the bytes) against
+// DevMaterial::transparent: upload_scene's any_transparent of the new mesh. One lane per material.
+__global__ __launch_bounds__(kBlock) void k_mesh_transparent(const uint8_t *__restrict__ used, const DevMaterial *__restrict__ mats,
+                                                             int32_t nm, MeshStatus *__restrict__ status) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (i < nm && used[i] && mats[i].transparent) atomicOr(&status->any_transparent, 1u);
+}
+
 // ---- GPU BVH build: Morton-order radix tree (RT_BUILD_LBVH; host statement: bvh.cpp build_lbvh) -------
 // Rule for every kernel here: no workgroup waits on another (no spin loops, flags or last-arriver walks);
 // atomics are counters or min/max; what one launch writes, only later launches read. Kernel boundaries
@@ -4381,6 +4417,17 @@ void launch_refit_tris(const RefitArgs &a, hipStream_t stream) {
     const int64_t n = std::max<int64_t>(a.nt, a.nv);
     if (n <= 0) return;
     hipLaunchKernelGGL(k_refit_tris, dim3(grid_for(n)), dim3(kBlock), 0, stream, a);
+}
+
+hipError_t launch_mesh_validate(const uint32_t *tri_v, const uint32_t *tri_mat, int32_t nt, int32_t nv, int32_t nm, const DevMaterial *mats,
+                                uint8_t *used, MeshStatus *status, hipStream_t stream) {
+    hipError_t e = hipMemsetAsync(status, 0, sizeof(MeshStatus), stream);
+    if (e == hipSuccess) e = hipMemsetAsync(used, 0, static_cast<size_t>(std::max(nm, 1)), stream);
+    if (e != hipSuccess || nt <= 0 || nm <= 0) return e;
+    hipLaunchKernelGGL(k_mesh_validate, dim3(grid_for(nt)), dim3(kBlock), 0, stream, tri_v, tri_mat, nt, static_cast<uint32_t>(nv),
+                       static_cast<uint32_t>(nm), used, status);
+    hipLaunchKernelGGL(k_mesh_transparent, dim3(grid_for(nm)), dim3(kBlock), 0, stream, used, mats, nm, status);
+    return hipGetLastError();
 }
 
 namespace {

@@ -14,6 +14,7 @@
 #   ab           same-box A/B of library builds (AB_LIBS: names of raytracert_amd/ab/lib_<name>.so, 'cur' = the
 #                in-tree build; AB_PASSES; AB_WORKLOADS; AB_ARGS extra bench arguments): the timed loop only
 #   refit        tools/refit_probe.py: update / re-create / frame times of C4 and C5 under a deformation
+#   set_mesh     tools/set_mesh_probe.py: rt_scene_set_mesh against destroy + create, C4 and C5
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"
 TAG=$1; shift
@@ -74,6 +75,9 @@ for STEP in "$@"; do
     refit)
       timeout -k 10 500 python -u tools/refit_probe.py profiles/refit_probe.json > $TMPDIR/refit_probe_$TAG.log 2>&1 || fail refit $TMPDIR/refit_probe_$TAG.log
       cat profiles/refit_probe.json ;;
+    set_mesh)
+      timeout -k 10 500 python -u tools/set_mesh_probe.py profiles/set_mesh_probe.json > $TMPDIR/set_mesh_probe_$TAG.log 2>&1 || fail set_mesh $TMPDIR/set_mesh_probe_$TAG.log
+      cat profiles/set_mesh_probe.json ;;
     *) echo "unknown step $STEP"; exit 2 ;;
   esac
 done
