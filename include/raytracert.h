@@ -261,7 +261,10 @@ int  rt_scene_create_ex(const float *xyz, int32_t n_vertices, const uint32_t *tr
 int rt_ray_intersect_triangle(int32_t device, const float *rays, const float *tris, int32_t n, uint8_t *hit,
                               float *points);
 /* Batched intersectMesh: n rays (origin[i], dest[i], host arrays of 3*n floats).
- * index_out[i] = closest triangle or -1; point_out[3*i..] = hit point or (0,0,0). */
+ * index_out[i] = closest triangle or -1; point_out[3*i..] = hit point or (0,0,0).
+ * Any float32 rays, here and in every ray entry below: the answer is the reference's bit for bit (no hit for a NaN
+ * or infinite component); only speed depends on the ray (|dest - origin| outside [2^-63, 2^63] walks without the
+ * distance cull, a ray long enough for n.dir to overflow meets every triangle). */
 int rt_intersect_mesh(rt_scene *scene, const float *origins, const float *dests, int32_t n,
                       int32_t *index_out, float *point_out);
 /* Batched performRayTracing: rgb_out[3*i..] = unclamped colour of ray i.

@@ -28,9 +28,23 @@
 //    every query tests them first (the "always" list). Triangles with n == 0 are rejected by
 //    isNullVector and never tested.
 //  * Box tests and the distance cull use relative slack (1e-5) far above their rounding error.
+//  * Domain: every float ray. The slab tests are conservative for any finite direction (components of
+//    +0 / -0 and below 2^-100 take a clamped reciprocal of their sign, which narrows a slab only where
+//    |n.dir| >= 1e-5 cannot hold) and any finite origin (the pad grows with |o|_1; past the scene's size
+//    every box is wanted). The distance cull turns best into a slab parameter through |dir|; it is used
+//    only when dot(dir, dir) is a positive normal float (|dir| within about [2^-63, 2^63]). Outside that,
+//    and for rays with a NaN or infinite component, the ray is walked with the slab tests alone (decided
+//    once per ray: ray4_setup and bvh_query in rt_kernels.hip), which skips no more than the slab
+//    argument allows. A ray so long that n.dir can overflow (32 M_1^2 max|dir_k| >= FLT_MAX) is outside any
+//    box argument: with b = +/-inf the reference takes r = 0 and I = o and accepts triangles by the origin's
+//    projection alone; such a ray is made to meet every triangle (ndir_may_overflow in rt_kernels.hip), the
+//    brute-force loop in tree order. A non-finite ray is accepted by no triangle (its distance is never below best), so
+//    any set of visited leaves gives the reference's "no hit"; a NaN slab compare skips the child, and a
+//    walk visits a node at most once whatever the floats are, so it ends.
 //
-// tests/test_bvh.py checks the acceptance claim directly against the oracle's arithmetic, and
-// tests/test_gpu_parity.py checks BVH results against brute force bit for bit.
+// tests/test_bvh.py checks the acceptance claim directly against the oracle's arithmetic,
+// tests/test_gpu_parity.py checks BVH results against brute force bit for bit, and
+// tests/test_gpu_edge_rays.py checks every walk against the oracle on the rays of the last item.
 #include <algorithm>
 #include <array>
 #include <atomic>

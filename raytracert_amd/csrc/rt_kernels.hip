@@ -261,6 +261,24 @@ constexpr int kBvhBlock = RT_BVH_BLOCK;
 // percent faster than the unconstrained ~80 VGPRs (6 waves); 8 waves spills and is not.
 
 struct RayBox { V3 o, inv; float pad, dlen; };
+constexpr int kPosNormal = 0x100;   // v_cmp_class_f32: a positive normal number
+
+// Rays so long that n.dir can overflow (test_triangle's b, raytracing.cpp:113). With b = +/-inf the
+// reference gets r = a / b = +/-0 and I = o: it accepts every triangle whose plane projection holds the
+// ORIGIN, at distance 0, wherever the ray goes, so no box argument applies and such a ray must meet every
+// triangle (the walks below then want every child: the brute-force loop in tree order, the same
+// lexicographic minimum). |n_k| <= 8 M1^2 for n = u x v with edges of vertices within M1 (scene_m1, the
+// largest |x| + |y| + |z|), so no product or partial sum of b overflows while 32 M1^2 max|dir_k| < FLT_MAX.
+// A NaN or infinite product compares false: wanted too. (A NaN direction component is dropped by fmaxf; a
+// non-finite ray is accepted by no triangle whatever is visited.)
+#ifndef RT_NDIR_GUARD
+#define RT_NDIR_GUARD 1   // 0: measurement only (the walks are then wrong for such rays)
+#endif
+__device__ __forceinline__ bool ndir_may_overflow(const DevScene &sc, V3 dir) {
+    if (!RT_NDIR_GUARD) return false;
+    const float dmax = fmaxf(fmaxf(fabsf(dir.x), fabsf(dir.y)), fabsf(dir.z));
+    return !(dmax * (32.0f * sc.scene_m1 * sc.scene_m1) < FLT_MAX);
+}
 
 // Per-lane traversal stack: the first `cap` entries in LDS ([entry][lane], conflict-free), deeper
 // entries in a global overflow area ([entry - cap][global lane], coalesced). Trees deeper than
@@ -419,7 +437,16 @@ __device__ __forceinline__ void bvh_query(const DevScene &sc, V3 o, V3 dir, bool
     R.o = o;
     R.inv = mk(1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z);
     R.pad = 64.0f * 5.9604645e-08f * (fabsf(o.x) + fabsf(o.y) + fabsf(o.z) + sc.scene_m1);
-    R.dlen = sqrtf(dot(dir, dir));
+    // The distance cull needs |dir| as a float. When dot(dir, dir) is not a positive normal number (|dir| above
+    // 2^63: +inf, so every child was culled and the walk found nothing beyond the always list; below 2^-63;
+    // a non-finite ray) the ray walks without it: dlen 0 makes the culled quantity -pad, never above best.
+    // (t = +inf, an axis with dir 0 and the origin outside that slab, gives NaN and is still skipped: that
+    // ray never enters the box.) Decided here, once per ray; every other ray's dlen is the same float.
+    const float dd = dot(dir, dir);
+    R.dlen = __builtin_amdgcn_class(dd, kPosNormal) ? sqrtf(dd) : 0.0f;
+    // a ray that must meet every triangle: an infinite pad makes every slab (-inf, +inf), so every child is
+    // wanted at entry 0 and the culled quantity is -inf
+    if (ndir_may_overflow(sc, dir)) R.pad = INFINITY;
     int sp = 0;
     int32_t ref = 0;
     while (true) {
@@ -690,6 +717,17 @@ __device__ __forceinline__ int32_t node4_next(const Ray4 &R, const Node4Rows &nd
 // the binary tree otherwise) no slab distance can be NaN (an empty slot's infinite bound gives
 // +/-inf, rejected), and a clamped axis only narrows a slab where no hit can exist (|n.dir| >= 1e-5
 // needs |dir| >= 2.5e-18 there).
+//
+// Which rays: any float ray. The slab test holds for every finite dir (a reciprocal that v_rcp_f32 flushes
+// to 0, |dir_k| above 2^126, makes that axis' slab always wanted). The distance cull needs 1 / |dir| as a
+// float: when dot(dir, dir) is not a positive normal number (|dir| above 2^63 overflows it, and v_rsq_f32
+// of +inf is 0, which made tcull 0 after the first hit, so the walk kept the first hit it found, not the
+// nearest; |dir| below 2^-63 underflows it; a non-finite ray) inv_dlen is +inf and tcull stays +inf (or NaN,
+// which fminf drops) whatever best is: that ray walks with the slab test alone. Decided here, once per ray;
+// every other ray's inv_dlen is the same float as before. A non-finite ray can make any slab NaN; a NaN
+// compare skips the child, no triangle accepts such a ray (its distance is never below best), and every walk
+// visits a node at most once whatever the floats are. A ray long enough for n.dir to overflow wants every
+// child (ndir_may_overflow, above). (tests/test_gpu_edge_rays.py)
 __device__ __forceinline__ void ray4_setup(const DevScene &sc, V3 o, V3 dir, Ray4 &R, float &pad) {
     V3 inv = mk(__builtin_amdgcn_rcpf(dir.x), __builtin_amdgcn_rcpf(dir.y), __builtin_amdgcn_rcpf(dir.z));
     constexpr float kInvMax = 0x1p100f;
@@ -697,8 +735,18 @@ __device__ __forceinline__ void ray4_setup(const DevScene &sc, V3 o, V3 dir, Ray
     if (!(fabsf(inv.y) <= kInvMax)) inv.y = copysignf(kInvMax, dir.y);
     if (!(fabsf(inv.z) <= kInvMax)) inv.z = copysignf(kInvMax, dir.z);
     pad = 64.0f * 5.9604645e-08f * (fabsf(o.x) + fabsf(o.y) + fabsf(o.z) + sc.scene_m1);
+    // a ray that must meet every triangle (ndir_may_overflow): the slab constants of inv 2^-126, origin 0 and
+    // pad 2^126, so every plane of a non-empty child is fma(b, 2^-126, -/+1) = -/+1 (|b| < 1e6 here): te = 0 <=
+    // tx = 1 and te <= tcull (never negative); an empty slot's +inf / -inf bounds still give te = +inf > tx = -inf
+    // (this walk serves scenes below 1e6, dev_view: 32 M1^2 < 2^45, so the bound of ndir_may_overflow is a constant)
+    if (RT_NDIR_GUARD && !(fmaxf(fmaxf(fabsf(dir.x), fabsf(dir.y)), fabsf(dir.z)) < 0x1p83f)) {
+        inv = mk(FLT_MIN, FLT_MIN, FLT_MIN);
+        o = mk(0, 0, 0);
+        pad = 0x1p126f;
+    }
     // 1.00001 / |dir| with v_rsq_f32 (1 ulp) rounded up by 1e-4: never below the division form
-    R.inv_dlen = __builtin_amdgcn_rsqf(dot(dir, dir)) * 1.00011f;
+    const float dd = dot(dir, dir);
+    R.inv_dlen = __builtin_amdgcn_class(dd, kPosNormal) ? __builtin_amdgcn_rsqf(dd) * 1.00011f : INFINITY;
     const bool nx = inv.x < 0, ny = inv.y < 0, nz = inv.z < 0;
     const float pnx = nx ? pad : -pad, pny = ny ? pad : -pad, pnz = nz ? pad : -pad;   // near = lo - pad / hi + pad
     R.ax = f2{inv.x, (pnx - o.x) * inv.x};
