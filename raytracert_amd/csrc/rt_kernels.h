@@ -81,9 +81,7 @@ struct ShadowSource {
 struct DevScene {
     const TriRec *tris;
     const uint32_t *tri_mat;
-    const float4 *normals;          // xyz = face normal; w = 1: ntab holds its normalize() states
-    const float4 *ntab;             // per face [N(n), N(N(n))] where N(N(N(n))) == N(n) bitwise (shade's
-                                    // repeated normal.normalize(), Vec3D.h:142-151), k_normal_table
+    const float4 *normals;          // xyz = face normal, w = 0
     const DevMaterial *mats;
     const uint32_t *ties;           // powf(x,2) tie table
     int32_t nt, nm, n_ties, any_transparent;
@@ -216,10 +214,6 @@ void launch_gen_rays_device(const void *org, const void *dst, int32_t ray_stride
                             hipStream_t stream);
 // calculateNormals on the device (face normal per triangle into normals[i].xyz)
 void launch_face_normals(const float *xyz, const uint32_t *tri_v, int32_t nt, float4 *normals, hipStream_t stream);
-// True when this build's test_triangle reads RN(1/D) from the records' D slot (RT_TRI_RCP): the
-// uploads then pass every record through tri_rcp_slot (rt_internal.h).
-bool tri_rcp_records();
-void launch_normal_table(float4 *normals, float4 *ntab, int32_t nt, hipStream_t stream);
 // ---- dynamic geometry (rt_scene_update_vertices) ----
 // What a refit reports back in one small read: the class-change count and build_bvh's m1 (the bits of a
 // non-negative double, maximised as an integer). Zeroed before launch_refit_tris.
@@ -237,12 +231,11 @@ struct RefitArgs {
     // of the always list, kRefitNeverSlot never accepted. Null: no tree (records and normals only).
     const int32_t *tri_slot;
     TriRec *tris, *leaf_recs, *always_recs;
-    float4 *normals, *ntab;
+    float4 *normals;
     float4 *slot_box;          // per leaf slot: the padded acceptance box (lo, hi)
     RefitStatus *status;
 };
-// One lane per triangle / vertex: records (tri_rcp_slot form when tri_rcp_records()), face normals, normal
-// table, acceptance boxes, classes, scene_m1 (k_refit_tris).
+// One lane per triangle / vertex: records, face normals, acceptance boxes, classes, scene_m1 (k_refit_tris).
 void launch_refit_tris(const RefitArgs &a, hipStream_t stream);
 // One height of a tree: ids[0..n) are its nodes; call in increasing height, one launch each.
 void launch_refit_level4(Bvh4F *nodes, const int32_t *ids, int32_t n, const float4 *slot_box, hipStream_t stream);

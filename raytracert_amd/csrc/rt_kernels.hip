@@ -156,22 +156,6 @@ __device__ __forceinline__ void sgpr_fence(const TriRec &T) {
 // kStages (the brute-force roofline's counting pass only): stg[k] += 1 for each stage the test reaches
 // (kTestStageFlops: 0 the plane terms, 1 the division, 2 the in-plane coordinates and s, 3 t, 4 the
 // distance), so the work a launch performed is counted, not a union path every test is assumed to take.
-#ifndef RT_TRI_RCP
-#define RT_TRI_RCP 0   // 1: measured no faster (profiles/r05zi_ab_tri_rcp.txt)
-#endif
-// The s and t divisions by D (:144, :148) from the record's reciprocal slot (RT_TRI_RCP, r05): the
-// uploaded records carry rD = RN(1/D) in D's place (NaN where |D| is outside [2^-30, 2^30] or D is
-// not normal; tri_rcp_slot) and D is recomputed from uu, uv, vv as the loader computes it (:140, the
-// same bits). With q = RN(n rD) in [2^-30, 2^30] every intermediate is normal, the residual
-// fma(-q, D, n) is exact and q + r rD rounds to the correctly rounded n / D (Markstein's correction;
-// tools/markstein_gpu.hip checks all 2^46 significand pairs); elsewhere (rD NaN, n near 0 or huge)
-// the lane divides. Five instructions instead of ~11 for both divisions of a test that reaches them.
-__device__ __forceinline__ float div_by_rec(float n, float D, float rD) {
-    const float q = n * rD;
-    if (__builtin_expect(fabsf(q) >= 0x1p-30f && fabsf(q) <= 0x1p30f, 1)) return fmaf(fmaf(-q, D, n), rD, q);
-    return n / D;
-}
-
 constexpr int kTestStages = 5;
 constexpr int kTestStageFlops[kTestStages] = {14, 1, 23, 5, 9};
 template <bool kAnyHit, bool kLex = false, bool kSignFirst = false, bool kStages = false>
@@ -192,19 +176,10 @@ __device__ __forceinline__ void test_triangle(const TriRec &T, int t, V3 o, V3 d
     const V3 w = mk(I.x - T.t0[0], I.y - T.t0[1], I.z - T.t0[2]);               // :137
     const float wu = w.x * T.u[0] + w.y * T.u[1] + w.z * T.u[2];                 // :138
     const float wv = w.x * T.v[0] + w.y * T.v[1] + w.z * T.v[2];                 // :139
-#if RT_TRI_RCP
-    const float D = T.uv * T.uv - T.uu * T.vv;                                  // :140 (T.D holds rD)
-    const float s = div_by_rec(T.uv * wv - T.vv * wu, D, T.D);                  // :144
-#else
     const float s = (T.uv * wv - T.vv * wu) / T.D;                              // :144
-#endif
     if (s < 0 || s > 1) return;                                                 // :145
     if (kStages) ++stg[3];
-#if RT_TRI_RCP
-    const float tt = div_by_rec(T.uv * wu - T.uu * wv, D, T.D);                 // :148
-#else
     const float tt = (T.uv * wu - T.uu * wv) / T.D;                             // :148
-#endif
     if (tt < 0 || (s + tt) > 1) return;                                         // :149
     if (kStages) ++stg[4];
     const V3 e = sub(o, I);                                                     // distance, Vec3D.h:199-202
@@ -271,11 +246,7 @@ constexpr int kPosNormal = 0x100;   // v_cmp_class_f32: a positive normal number
 // largest |x| + |y| + |z|), so no product or partial sum of b overflows while 32 M1^2 max|dir_k| < FLT_MAX.
 // A NaN or infinite product compares false: wanted too. (A NaN direction component is dropped by fmaxf; a
 // non-finite ray is accepted by no triangle whatever is visited.)
-#ifndef RT_NDIR_GUARD
-#define RT_NDIR_GUARD 1   // 0: measurement only (the walks are then wrong for such rays)
-#endif
 __device__ __forceinline__ bool ndir_may_overflow(const DevScene &sc, V3 dir) {
-    if (!RT_NDIR_GUARD) return false;
     const float dmax = fmaxf(fmaxf(fabsf(dir.x), fabsf(dir.y)), fabsf(dir.z));
     return !(dmax * (32.0f * sc.scene_m1 * sc.scene_m1) < FLT_MAX);
 }
@@ -367,13 +338,9 @@ __device__ __forceinline__ bool box_hit(const RayBox &R, float lx, float ly, flo
 
 // The always list (ill-conditioned triangles, bvh.cpp): every query tests them. Their records are
 // gathered contiguously (always_recs) and streamed like the brute-force loop: wave-uniform,
-// two records alternating so one load is in flight behind the arithmetic.
-#ifndef RT_LEAF_SIGN
-#define RT_LEAF_SIGN 0     // the same in the walks' leaf loops
-#endif
-#ifndef RT_ALWAYS_SIGN
-#define RT_ALWAYS_SIGN 1   // the always-tested list (uniform records, coherent rays) rejects r < 0 by signs first
-#endif
+// two records alternating so one load is in flight behind the arithmetic. Its tests reject r < 0 by
+// signs first (kSignFirst: uniform records, coherent rays); the walks' leaf loops do not (their lanes
+// hold different triangles, so every test would pay the check: measured 2% slower on C4).
 template <bool kAnyHit>
 __device__ __forceinline__ void test_always(const DevScene &sc, V3 o, V3 dir, float &best, int &bidx, V3 &bI,
                                             bool &done) {
@@ -386,14 +353,14 @@ __device__ __forceinline__ void test_always(const DevScene &sc, V3 o, V3 dir, fl
         if (kAnyHit && (i & 15) == 0 && __all(done)) return;
         sgpr_fence(A);
         const TriRec B = recs[i + 1];
-        test_triangle<kAnyHit, true, RT_ALWAYS_SIGN>(A, static_cast<int>(sc.always[i]), o, dir, best, bidx, bI, done);
+        test_triangle<kAnyHit, true, true>(A, static_cast<int>(sc.always[i]), o, dir, best, bidx, bI, done);
         sgpr_fence(B);
         A = recs[min(i + 2, n - 1)];
-        test_triangle<kAnyHit, true, RT_ALWAYS_SIGN>(B, static_cast<int>(sc.always[i + 1]), o, dir, best, bidx, bI, done);
+        test_triangle<kAnyHit, true, true>(B, static_cast<int>(sc.always[i + 1]), o, dir, best, bidx, bI, done);
     }
     if (i < n) {
         sgpr_fence(A);
-        test_triangle<kAnyHit, true, RT_ALWAYS_SIGN>(A, static_cast<int>(sc.always[i]), o, dir, best, bidx, bI, done);
+        test_triangle<kAnyHit, true, true>(A, static_cast<int>(sc.always[i]), o, dir, best, bidx, bI, done);
     }
 }
 
@@ -401,25 +368,9 @@ __device__ __forceinline__ void test_always(const DevScene &sc, V3 o, V3 dir, fl
 // reaches the comparison with the current best.
 // (Skipping the divisions when their outcome is decided by signs or approximate quotients was
 // measured slower: the extra branches and registers cost more than the divisions they save.)
-#ifndef RT_LEAF_PAIRS
-#define RT_LEAF_PAIRS 0   // measured neutral on C4 (0.88 vs 0.89 ms), costs VGPRs
-#endif
 template <bool kAnyHit>
 __device__ __forceinline__ void test_leaf(const DevScene &sc, int first, int cnt, V3 o, V3 dir, float &best, int &bidx,
                                           V3 &bI, bool &done) {
-    if (RT_LEAF_PAIRS) {
-        // Two records per round, both loads in flight before either test (the second load repeats
-        // the last record when the count is odd; its test is skipped). The lexicographic minimum
-        // does not depend on the order of the tests.
-        for (int k = 0; k < cnt; k += 2) {
-            const int k1 = min(k + 1, cnt - 1);
-            const TriRec A = leaf_rec(sc, first + k);
-            const TriRec B = leaf_rec(sc, first + k1);
-            test_triangle<kAnyHit, true>(A, static_cast<int>(sc.leaf_idx[first + k]), o, dir, best, bidx, bI, done);
-            if (k1 != k) test_triangle<kAnyHit, true>(B, static_cast<int>(sc.leaf_idx[first + k1]), o, dir, best, bidx, bI, done);
-        }
-        return;
-    }
     for (int k = 0; k < cnt; ++k) {
         const TriRec T = leaf_rec(sc, first + k);
         test_triangle<kAnyHit, true>(T, static_cast<int>(sc.leaf_idx[first + k]), o, dir, best, bidx, bI, done);
@@ -516,31 +467,9 @@ constexpr int32_t kDoneRef = kBvhEmpty;   // "no ref": a count-0 leaf is never a
 // for the plane's float bound b (Bvh4F), instead of (b -/+ pad - o) * inv: the same value up to a few
 // ulps of (|o| + pad) * |inv| and of |t|, inside the pad (64 ulps of |o| + the scene's extent) and the
 // 1e-5 relative slack of the te <= tx test.
-//
-// The six planes of two children are one v_pk_fma_f32 each (r04): a row's float4 is two register
-// pairs, and op_sel / op_sel_hi broadcast one half of a per-ray pair to both elements, so the
-// per-ray constants live in five pairs with no splat copies. Per element the packed FMA is the
-// same IEEE fused multiply-add as v_fma_f32 (same rounding and denormal mode), so every slab
-// parameter has the bits of the scalar form.
-#ifndef RT_PK_BOX
-#define RT_PK_BOX 0   // measured: VALU -5% but C4 +1-2% (profiles/r04_ab_pk_box.txt); kept for the record
-#endif
+// The constants sit in five register pairs: the layout of the packed-FMA plane evaluation that was
+// measured and removed; the scalar FMAs below read the halves.
 typedef float f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f2 pk_fma_xy(f2 a, f2 s) {          // a * s.x + s.y, both elements
-    f2 d;
-    asm("v_pk_fma_f32 %0, %1, %2, %2 op_sel:[0,0,1] op_sel_hi:[1,0,1]" : "=v"(d) : "v"(a), "v"(s));
-    return d;
-}
-__device__ __forceinline__ f2 pk_fma_x_x(f2 a, f2 s, f2 t) {   // a * s.x + t.x
-    f2 d;
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(a), "v"(s), "v"(t));
-    return d;
-}
-__device__ __forceinline__ f2 pk_fma_x_y(f2 a, f2 s, f2 t) {   // a * s.x + t.y
-    f2 d;
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,1] op_sel_hi:[1,0,1]" : "=v"(d) : "v"(a), "v"(s), "v"(t));
-    return d;
-}
 struct Ray4 {
     f2 ax, ay, az;   // per axis (inv, (+/-pad - o) * inv of the near plane)
     f2 fxy;          // (+/-pad - o) * inv of the far planes x, y
@@ -556,27 +485,10 @@ __device__ __forceinline__ float cull_param(const Ray4 &R, float best, float pad
     return (best * 1.00002f + pad) * R.inv_dlen;
 }
 
-#ifndef RT_LIM_ASM
-#define RT_LIM_ASM 0   // min(tx (1 + 1e-5), tcull) as v_min_f32 in asm: compiled fminf re-canonicalises tcull each visit
-#endif
-#ifndef RT_ALWAYS_SORT
-#define RT_ALWAYS_SORT 0   // closest-hit: sort every node's keys (no nh count, no one-child branch)
-#endif
-#ifndef RT_ANY_ORDER
-#define RT_ANY_ORDER 0   // any-hit child order: 0 index order, 1 nearest entry first, 2 farthest first
-#endif
-#ifndef RT_TX_SLACK
-#define RT_TX_SLACK 1   // the 1e-5 relative slack of te <= tx (0: A/B measurement only)
-#endif
 template <bool kAnyHit>
 __device__ __forceinline__ float node_lim(float tx, float tcull) {
-    const float txs = RT_TX_SLACK ? tx * 1.00001f : tx;
+    const float txs = tx * 1.00001f;   // the 1e-5 relative slack of te <= tx
     if (kAnyHit) return txs;
-    if (RT_LIM_ASM) {
-        float lim;
-        asm("v_min_f32 %0, %1, %2" : "=v"(lim) : "v"(txs), "v"(tcull));
-        return lim;
-    }
     return fminf(txs, tcull);
 }
 
@@ -594,28 +506,6 @@ __device__ __forceinline__ int32_t node4_next(const Ray4 &R, const Node4Rows &nd
     const float tcull = R.fzc.y;
     int32_t rc[4] = {nd.ref.x, nd.ref.y, nd.ref.z, nd.ref.w};
     float tc[4];
-#if RT_PK_BOX
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {   // children 2h, 2h + 1
-        const f2 nx = h ? f2{nd.n[0].z, nd.n[0].w} : f2{nd.n[0].x, nd.n[0].y};
-        const f2 ny = h ? f2{nd.n[1].z, nd.n[1].w} : f2{nd.n[1].x, nd.n[1].y};
-        const f2 nz = h ? f2{nd.n[2].z, nd.n[2].w} : f2{nd.n[2].x, nd.n[2].y};
-        const f2 fx = h ? f2{nd.f[0].z, nd.f[0].w} : f2{nd.f[0].x, nd.f[0].y};
-        const f2 fy = h ? f2{nd.f[1].z, nd.f[1].w} : f2{nd.f[1].x, nd.f[1].y};
-        const f2 fz = h ? f2{nd.f[2].z, nd.f[2].w} : f2{nd.f[2].x, nd.f[2].y};
-        const f2 a = pk_fma_xy(nx, R.ax), b = pk_fma_xy(ny, R.ay), c = pk_fma_xy(nz, R.az);
-        const f2 d = pk_fma_x_x(fx, R.ax, R.fxy), e = pk_fma_x_y(fy, R.ay, R.fxy), f = pk_fma_x_x(fz, R.az, R.fzc);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            // max(tnx, tny, tnz, 0) and min(tfx, tfy, tfz) as v_max3/v_min3 on the packed results
-            // (compiled fmaxf/fminf would first canonicalise each asm output: no NaN reaches here)
-            float te, tx;
-            asm("v_max3_f32 %0, %1, %2, %3\n\tv_max_f32 %0, 0, %0" : "=&v"(te) : "v"(j ? a.y : a.x), "v"(j ? b.y : b.x), "v"(j ? c.y : c.x));
-            asm("v_min3_f32 %0, %1, %2, %3" : "=v"(tx) : "v"(j ? d.y : d.x), "v"(j ? e.y : e.x), "v"(j ? f.y : f.x));
-            tc[2 * h + j] = te <= node_lim<kAnyHit>(tx, tcull) ? te : INFINITY;
-        }
-    }
-#else
     {
         const float nx[4] = {nd.n[0].x, nd.n[0].y, nd.n[0].z, nd.n[0].w}, fx[4] = {nd.f[0].x, nd.f[0].y, nd.f[0].z, nd.f[0].w};
         const float ny[4] = {nd.n[1].x, nd.n[1].y, nd.n[1].z, nd.n[1].w}, fy[4] = {nd.f[1].x, nd.f[1].y, nd.f[1].z, nd.f[1].w};
@@ -630,33 +520,11 @@ __device__ __forceinline__ int32_t node4_next(const Ray4 &R, const Node4Rows &nd
             tc[k] = te <= node_lim<kAnyHit>(tx, tcull) ? te : INFINITY;
         }
     }
-#endif
     if (!kAnyHit) {
         // Sorted, branch-free pushes: the wanted children after the first go to the stack with
         // unconditional LDS writes when every lane's stack has room (slots past the new top are
         // scratch); pops the same way. Misses are INFINITY and sort last.
         const int lane = static_cast<int>(threadIdx.x);
-        if (RT_ALWAYS_SORT) {
-            cswap(tc[0], rc[0], tc[1], rc[1]);
-            cswap(tc[2], rc[2], tc[3], rc[3]);
-            cswap(tc[0], rc[0], tc[2], rc[2]);
-            cswap(tc[1], rc[1], tc[3], rc[3]);
-            cswap(tc[1], rc[1], tc[2], rc[2]);
-            // the wanted children are a prefix of the sorted keys
-            const bool w1 = tc[1] != INFINITY, w2 = tc[2] != INFINITY, w3 = tc[3] != INFINITY;
-            if (__all(sp + 3 <= stack.cap)) {
-                stack.lds[sp * stack.width + lane] = w3 ? rc[3] : w2 ? rc[2] : rc[1];
-                stack.lds[(sp + 1) * stack.width + lane] = w3 ? rc[2] : rc[1];
-                stack.lds[(sp + 2) * stack.width + lane] = rc[1];
-                sp += static_cast<int>(w1) + static_cast<int>(w2) + static_cast<int>(w3);
-            } else {
-                if (w3) stack.push(sp, rc[3]);
-                if (w2) stack.push(sp, rc[2]);
-                if (w1) stack.push(sp, rc[1]);
-            }
-            if (tc[0] != INFINITY) return rc[0];
-            return stack.pop_or(sp, base, kDoneRef);
-        }
         const int nh = (tc[0] != INFINITY) + (tc[1] != INFINITY) + (tc[2] != INFINITY) + (tc[3] != INFINITY);
         if (nh > 1) {   // (the 5-exchange network costs ~25 VALU; nodes with one child or none skip it)
             cswap(tc[0], rc[0], tc[1], rc[1]);
@@ -681,20 +549,6 @@ __device__ __forceinline__ int32_t node4_next(const Ray4 &R, const Node4Rows &nd
         return stack.pop_or(sp, base, kDoneRef);
     }
     // any-hit: any order finds the same verdict; visit the first wanted child, push the others
-#if RT_ANY_ORDER
-    {   // visit the nearest (1) or farthest (2) wanted child first, push the others
-        int kb = -1;
-        float tb = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (tc[k] != INFINITY && (kb < 0 || (RT_ANY_ORDER == 1 ? tc[k] < tb : tc[k] > tb))) { kb = k; tb = tc[k]; }
-#pragma unroll
-        for (int k = 3; k >= 0; --k)
-            if (tc[k] != INFINITY && k != kb) stack.push(sp, rc[k]);
-        if (kb >= 0) return rc[kb];
-        return stack.pop_or(sp, base, kDoneRef);
-    }
-#endif
     int32_t nxt = kDoneRef;
     bool have = false;
 #pragma unroll
@@ -739,7 +593,7 @@ __device__ __forceinline__ void ray4_setup(const DevScene &sc, V3 o, V3 dir, Ray
     // pad 2^126, so every plane of a non-empty child is fma(b, 2^-126, -/+1) = -/+1 (|b| < 1e6 here): te = 0 <=
     // tx = 1 and te <= tcull (never negative); an empty slot's +inf / -inf bounds still give te = +inf > tx = -inf
     // (this walk serves scenes below 1e6, dev_view: 32 M1^2 < 2^45, so the bound of ndir_may_overflow is a constant)
-    if (RT_NDIR_GUARD && !(fmaxf(fmaxf(fabsf(dir.x), fabsf(dir.y)), fabsf(dir.z)) < 0x1p83f)) {
+    if (!(fmaxf(fmaxf(fabsf(dir.x), fabsf(dir.y)), fabsf(dir.z)) < 0x1p83f)) {
         inv = mk(FLT_MIN, FLT_MIN, FLT_MIN);
         o = mk(0, 0, 0);
         pad = 0x1p126f;
@@ -757,14 +611,6 @@ __device__ __forceinline__ void ray4_setup(const DevScene &sc, V3 o, V3 dir, Ray
     constexpr uint32_t kLo = offsetof(Bvh4F, lo), kHi = offsetof(Bvh4F, hi), kRow = sizeof(float4);
     R.rows[0] = (nx ? kHi : kLo); R.rows[1] = (ny ? kHi : kLo) + kRow; R.rows[2] = (nz ? kHi : kLo) + 2 * kRow;
     R.rows[3] = (nx ? kLo : kHi); R.rows[4] = (ny ? kLo : kHi) + kRow; R.rows[5] = (nz ? kLo : kHi) + 2 * kRow;
-}
-
-#ifndef RT_POP_FAST
-#define RT_POP_FAST 1   // the walks' own pops (postponement, leaf loop) through LaneStack::pop_or
-#endif
-__device__ __forceinline__ int32_t walk_pop(const LaneStack &stack, int &sp, int base) {
-    if (RT_POP_FAST) return stack.pop_or(sp, base, kDoneRef);
-    return sp > base ? stack.pop(sp) : kDoneRef;
 }
 
 template <bool kAnyHit>
@@ -786,7 +632,7 @@ __device__ __forceinline__ void bvh4_query_ww(const DevScene &sc, V3 o, V3 dir, 
             node = node4_next<kAnyHit>(R, load_node4(sc.nodes4f, node, R.rows), stack, sp);
             if (node < 0 && node != kDoneRef && leaf == kDoneRef) {   // postpone it, keep walking
                 leaf = node;
-                node = walk_pop(stack, sp, 0);
+                node = stack.pop_or(sp, 0, kDoneRef);
             }
             if (__all(leaf != kDoneRef)) break;   // every lane still walking holds a leaf
         }
@@ -797,7 +643,7 @@ __device__ __forceinline__ void bvh4_query_ww(const DevScene &sc, V3 o, V3 dir, 
             // one triangle per iteration: the ref is the cursor (first + 1, count - 1), so a lane
             // whose leaf ends goes on to its next leaf while the others test their next triangle
             const TriRec T = leaf_rec(sc, first);
-            test_triangle<kAnyHit, true, RT_LEAF_SIGN>(T, static_cast<int>(sc.leaf_idx[first]), o, dir, best, bidx, bI, done);
+            test_triangle<kAnyHit, true>(T, static_cast<int>(sc.leaf_idx[first]), o, dir, best, bidx, bI, done);
             ++tests;
             if (kAnyHit && done) { node = kDoneRef; break; }
             if (cnt > 1) {
@@ -808,7 +654,7 @@ __device__ __forceinline__ void bvh4_query_ww(const DevScene &sc, V3 o, V3 dir, 
             leaf = kDoneRef;
             if (node < 0 && node != kDoneRef) {
                 leaf = node;
-                node = walk_pop(stack, sp, 0);
+                node = stack.pop_or(sp, 0, kDoneRef);
             }
         }
         if (node == kDoneRef) break;
@@ -816,7 +662,7 @@ __device__ __forceinline__ void bvh4_query_ww(const DevScene &sc, V3 o, V3 dir, 
 }
 // ---------------------------------------------------------------------------------------------
 // While-while walk with in-wave work stealing (RT_TUNE_WAVE_STEAL, chain launch): a lane whose own query is finished
-// takes the bottom entry of another lane's traversal stack (a subtree that lane would visit later)
+// takes the top entry of another lane's traversal stack (that lane's nearest pending subtree)
 // together with that lane's ray, walks it with the same node and triangle arithmetic, and folds
 // what it finds into the ray owner's (distance, index) key in LDS. Exactness: every subtree is
 // walked by exactly one lane; a helper culls with its own best, which starts at the donor's best
@@ -836,9 +682,6 @@ __device__ __forceinline__ void bvh4_query_ww(const DevScene &sc, V3 o, V3 dir, 
 // (how many of the longest batches run as half or quarter waves: RT_TUNE_STEAL_HALF / _QUARTER)
 #ifndef RT_STEAL_SPLIT_DIV
 #define RT_STEAL_SPLIT_DIV 32   // ... and at most this fraction (1 / DIV) of them
-#endif
-#ifndef RT_STEAL_TOP
-#define RT_STEAL_TOP 1        // 1: a donor gives its nearest pending subtree (top of stack); 0: its farthest
 #endif
 constexpr unsigned long long kNoKey = ~0ull;
 __device__ __forceinline__ unsigned long long hit_key(float best, int bidx) {
@@ -897,13 +740,8 @@ __device__ __forceinline__ void bvh4_query_steal(const DevScene &sc, V3 o, V3 di
             const int ir = rank_below(idle), dr = rank_below(donors);
             if (((donors >> lane) & 1ull) && dr < np) {
                 s_xfer[wb + 2 * dr] = lane | (owner << 8);
-                if (RT_STEAL_TOP) {   // the top entry: the nearest subtree still pending
-                    --sp;
-                    s_xfer[wb + 2 * dr + 1] = stack.at(sp);
-                } else {              // the bottom entry: the farthest
-                    s_xfer[wb + 2 * dr + 1] = stack.at(base);
-                    ++base;
-                }
+                --sp;   // the top entry: the nearest subtree still pending
+                s_xfer[wb + 2 * dr + 1] = stack.at(sp);
             }
             __builtin_amdgcn_wave_barrier();
             const bool helper = ((idle >> lane) & 1ull) && ir < np;
@@ -936,7 +774,7 @@ __device__ __forceinline__ void bvh4_query_steal(const DevScene &sc, V3 o, V3 di
             node = node4_next<kAnyHit>(R, load_node4(sc.nodes4f, node, R.rows), stack, sp, base);
             if (node < 0 && node != kDoneRef && leaf == kDoneRef) {   // postpone it, keep walking
                 leaf = node;
-                node = walk_pop(stack, sp, base);
+                node = stack.pop_or(sp, base, kDoneRef);
             }
             if (__all(leaf != kDoneRef)) break;
         }
@@ -945,7 +783,7 @@ __device__ __forceinline__ void bvh4_query_steal(const DevScene &sc, V3 o, V3 di
             const int cnt = static_cast<int>((u >> kBvhCountShift) & kBvhCountMask);
             const int first = static_cast<int>(u & ((1u << kBvhCountShift) - 1u));
             const TriRec T = leaf_rec(sc, first);
-            test_triangle<kAnyHit, true, RT_LEAF_SIGN>(T, static_cast<int>(sc.leaf_idx[first]), o, dir, best, bidx, bI, done);
+            test_triangle<kAnyHit, true>(T, static_cast<int>(sc.leaf_idx[first]), o, dir, best, bidx, bI, done);
             ++tests;
             if (kAnyHit && done) { node = kDoneRef; leaf = kDoneRef; break; }
             if (cnt > 1) {
@@ -956,7 +794,7 @@ __device__ __forceinline__ void bvh4_query_steal(const DevScene &sc, V3 o, V3 di
             leaf = kDoneRef;
             if (node < 0 && node != kDoneRef) {
                 leaf = node;
-                node = walk_pop(stack, sp, base);
+                node = stack.pop_or(sp, base, kDoneRef);
             }
         }
     }
@@ -1089,7 +927,7 @@ __device__ __forceinline__ int32_t node4_next_quad(const Ray4 &R, const Bvh4F *_
 template <bool kAnyHit>
 __device__ __forceinline__ void test_always_quad(const DevScene &sc, V3 o, V3 dir, float &best, int &bidx, V3 &bI, bool &done, int q) {
     for (int i = q; i < sc.n_always; i += 4)
-        test_triangle<kAnyHit, true, RT_ALWAYS_SIGN>(sc.always_recs[i], static_cast<int>(sc.always[i]), o, dir, best, bidx, bI, done);
+        test_triangle<kAnyHit, true, true>(sc.always_recs[i], static_cast<int>(sc.always[i]), o, dir, best, bidx, bI, done);
 }
 
 template <bool kAnyHit>
@@ -1123,7 +961,7 @@ __device__ __forceinline__ void bvh4_query_quad(const DevScene &sc, V3 o, V3 dir
                 const int cnt = static_cast<int>((u >> kBvhCountShift) & kBvhCountMask);
                 const int first = static_cast<int>(u & ((1u << kBvhCountShift) - 1u));
                 for (int k = q; k < cnt; k += 4) {
-                    test_triangle<kAnyHit, true, RT_LEAF_SIGN>(leaf_rec(sc, first + k), static_cast<int>(sc.leaf_idx[first + k]), o, dir,
+                    test_triangle<kAnyHit, true>(leaf_rec(sc, first + k), static_cast<int>(sc.leaf_idx[first + k]), o, dir,
                                                                best, bidx, bI, done);
                     ++tests;
                 }
@@ -1800,17 +1638,14 @@ struct Secondary {
 // of every step: bytes written past L2 265 -> 104 MB per C4 launch, time unchanged.)
 constexpr uint32_t kCoefTr = 4u;
 
-// A chain record store. RT_CHAIN_SC1 (A/B build): written through past L2 (sc1), so the records,
-// read back once when the chain is folded, do not evict scene lines from the XCD's L2.
-#ifndef RT_CHAIN_SC1
-#define RT_CHAIN_SC1 1   // measured ~1.5% faster C4 frame (0.520 vs 0.528 ms)
-#endif
+// A chain record store: written through past L2 (sc1), so the records, read back once when the chain
+// is folded, do not evict scene lines from the XCD's L2 (measured ~1.5% faster C4 frame, 0.520 vs 0.528 ms).
 // The asm form exists on gfx94x/gfx950 only (this library is built for gfx950); the compiler does
 // not count the asm store in its vmcnt bookkeeping, which only makes its later waits stricter
 // (vector memory operations complete in order), and the s_nop covers the store-data hazard.
 __device__ __forceinline__ void store_chain(float4 *p, float4 v) {
 #if defined(__gfx942__) || defined(__gfx950__)
-    constexpr bool kSc1Asm = RT_CHAIN_SC1;
+    constexpr bool kSc1Asm = true;
 #else
     constexpr bool kSc1Asm = false;
 #endif
@@ -1865,23 +1700,6 @@ __device__ __forceinline__ void offset_point(V3 &point, V3 dest) {   // addOffse
 // record (local colour and child state, the child's coefficient, the depth when the chain ends)
 // and returns the secondary ray, if any. ray = dest - origin of the traced ray (:393);
 // is_shadowed(l) is isShadow's verdict for light l.
-#ifndef RT_HOIST_VIEW
-#define RT_HOIST_VIEW 1   // r04 one frame per launch: C4 equal, C5 6.85 -> 6.89 ms (profiles/r04_ab_hoist_view.txt);
-                          // r05 multi-frame launches (VALU-bound): C4 0.3398 -> 0.3395, C5 6.637 -> 6.589 ms
-                          // (profiles/r05o_ab_shade.txt)
-#endif
-#ifndef RT_HOIST_LNORM
-#define RT_HOIST_LNORM 1   // diffuse's normalize(light position) from ShadeParams::lnorm (made on the host)
-#endif
-#ifndef RT_PAIR_CLOSEST
-#define RT_PAIR_CLOSEST 1  // paired shadow helpers also in the closest-hit-shadow instantiations (scenes with transparency)
-#endif
-#ifndef RT_NORMAL_TABLE
-#define RT_NORMAL_TABLE 0  // the hit normal's normalize() states from DevScene::ntab (k_normal_table). Measured
-                           // (multi-frame launches): C5 (4 lights) 6.594 -> 6.566 ms, C4 (2 lights) 0.3400 ->
-                           // 0.3410 ms (profiles/r05p_ab_normal_table.txt): the table's loads cost about what the
-                           // normalisations did at 2 lights; off for the C4 headline
-#endif
 template <bool kInLane = false, bool kExtLights = true, typename Shadowed>
 __device__ __forceinline__ Secondary shade_hit(const DevScene &sc, const ShadeParams &p, const DevWork &w, int step,
                                                int sample, V3 ray, int lvl, int idx, V3 P,
@@ -1894,13 +1712,6 @@ __device__ __forceinline__ Secondary shade_hit(const DevScene &sc, const ShadePa
     const int64_t ci = static_cast<int64_t>(step) * w.rec_cap + sample, cc = static_cast<int64_t>(step) * w.cap + sample;
     const float4 nw = sc.normals[idx];
     V3 normal = ld3(nw);                                             // :394 (copy, mutated below)
-    // normal.normalize() (:199, :213): from the face's tabled states when it has them (k_normal_table)
-    const bool tabled = RT_NORMAL_TABLE && nw.w != 0.0f;
-    int nstate = 0;
-    auto renormalize = [&]() {
-        if (tabled) { nstate ^= 1; normal = ld3(sc.ntab[2 * static_cast<int64_t>(idx) + (nstate ? 0 : 1)]); }
-        else normalize(normal);
-    };
     const uint32_t mi = sc.tri_mat[idx];
     const DevMaterial m = sc.mats[mi];                               // :396
     uint32_t kind = 0;
@@ -1911,11 +1722,10 @@ __device__ __forceinline__ Secondary shade_hit(const DevScene &sc, const ShadePa
     V3 color = mk(0, 0, 0);                                          // :336
     if ((f & RT_AMBIENT) && (m.flags & RT_HAS_KA)) color = add(color, Ka);   // :337-340
     // specular's view vector (:213-215) depends on neither the light nor the normal: the same bits for
-    // every light, so RT_HOIST_VIEW 1 makes it once per hit (default 0: per light, as the loop is
-    // written; holding it across the light loop measured slower)
+    // every light, so it is made once per hit (multi-frame launches: C5 6.637 -> 6.589 ms, C4 equal)
     const bool spec_on = (f & RT_SPECULAR) && (m.flags & RT_HAS_KS) && (m.flags & RT_HAS_NS);
     V3 Vh = mk(0, 0, 0);
-    if (RT_HOIST_VIEW && spec_on && p.n_lights > 0) {
+    if (spec_on && p.n_lights > 0) {
         Vh = sub(mk(p.cam[0], p.cam[1], p.cam[2]), P);
         normalize(Vh);
     }
@@ -1925,9 +1735,9 @@ __device__ __forceinline__ Secondary shade_hit(const DevScene &sc, const ShadePa
         if (shadowed) continue;
         if ((f & RT_DIFFUSE) && (m.flags & RT_HAS_KD)) {             // diffuseOnly :197-205
             V3 diffuse = mk(0, 0, 0);
-            renormalize();
+            normalize(normal);                                       // :199, :213
             V3 lp = L;
-            if (RT_HOIST_LNORM && (!kExtLights || l < RT_MAX_LIGHTS)) lp = mk(p.lnorm[l][0], p.lnorm[l][1], p.lnorm[l][2]);
+            if (!kExtLights || l < RT_MAX_LIGHTS) lp = mk(p.lnorm[l][0], p.lnorm[l][1], p.lnorm[l][2]);
             else normalize(lp);
             diffuse = add(diffuse, scale(Kd, max_std(dot(normal, lp), 0.0f)));
             color = add(color, scale(diffuse, m.Tr));                // :349
@@ -1935,9 +1745,7 @@ __device__ __forceinline__ Secondary shade_hit(const DevScene &sc, const ShadePa
         if (spec_on) {                                               // :210-232
             V3 spec = mk(0, 0, 0);
             V3 Vv = Vh;
-            if (!RT_HOIST_VIEW) Vv = sub(mk(p.cam[0], p.cam[1], p.cam[2]), P);
-            renormalize();
-            if (!RT_HOIST_VIEW) normalize(Vv);
+            normalize(normal);                                       // :199, :213
             V3 Lv = sub(L, P);
             normalize(Lv);
             V3 H = add(Vv, Lv);
@@ -2118,34 +1926,18 @@ constexpr int kChainSteps = 256;   // max_lvl <= 254
 // they take the owner's hit by lane shuffles and walk lights r, r + roles, ... while the owner walks
 // lights 0, roles, ...; the owner ORs their verdicts into its mask and shades. Each light's walk is
 // the same walk on the same ray whichever lane runs it, so the mask is the same bits.
-// RT_LDS_PARK (A/B build): the step's values that only shading needs (the ray, lvl, the sample) wait
-// in LDS ([word][lane] beside the traversal stack) while the walks run, so they hold no VGPRs there.
-#ifndef RT_LDS_PARK
-#define RT_LDS_PARK 0
-#endif
-// RT_OPAQUE_ARGS 1 (default, r04): the chain kernel reads its frame geometry, shading parameters,
+// Opaque arguments (RT_OPAQUE_ARGS, r04): the chain kernel reads its frame geometry, shading parameters,
 // scene and workspace per wave batch through the kernel-argument pointer instead of holding them from
 // its start: 232 SGPRs had spilled into four VGPRs' lanes and pushed 48 B per lane into scratch;
 // now 72 and 24 B. C4 0.361 -> 0.348 ms per frame, C5 6.86 -> 6.68 ms, VALU -5.7%, WRITE_SIZE
-// 116 -> 72 MB per launch (profiles/r04_ab_opaque_args.txt). 0: the arguments as the compiler places them.
-// 2: the launch's scalar arguments (outputs, first step, split tiers) too: within the spread
-// (profiles/r04_ab_opaque_args2.txt).
-#ifndef RT_OPAQUE_ARGS
-#define RT_OPAQUE_ARGS 1
-#endif
-
-constexpr int kParkWords = 8;   // words per lane of the park area: ray xyz, lvl, sample, pixel (k_chain)
-struct Park {
-    float *base;   // [kParkWords][kBvhBlock] in LDS, or null
-    __device__ __forceinline__ void put(int k, float v) const { base[k * kBvhBlock + static_cast<int>(threadIdx.x)] = v; }
-    __device__ __forceinline__ float get(int k) const { return base[k * kBvhBlock + static_cast<int>(threadIdx.x)]; }
-};
+// 116 -> 72 MB per launch (profiles/r04_ab_opaque_args.txt). Reading the launch's scalar arguments
+// (outputs, first step, split tiers) that way too measured within the spread (profiles/r04_ab_opaque_args2.txt).
 
 template <bool kAnyHit, int W, bool kCount, bool kInLane = false, bool kSteal = false>
 __device__ __forceinline__ Secondary chain_step(const DevScene &sc, const ShadeParams &p, const DevWork &w, int step,
                                                 int sample, V3 org, V3 dst, int lvl, const LaneStack &stack, int *s_sh,
                                                 WorkTally<kCount> &wc, WorkTally<kCount> &ws, bool live = true,
-                                                bool pair = false, Park park = Park{nullptr}) {
+                                                bool pair = false) {
     // kPair (the fused in-lane launch): every lane of the wave calls this at every step of its batch,
     // live or not (live: this lane's chain traces a ray at this step); with `pair`, once the closest
     // hits are known the lanes without a hit (chain ended, missed, or no sample) help the lanes with
@@ -2153,17 +1945,13 @@ __device__ __forceinline__ Secondary chain_step(const DevScene &sc, const ShadeP
     // G = min(L - 1, nd / nh) helpers (the same G for all, so the shadow phase is uniform), the group
     // walking lights role, role + G + 1, ... Each (hit, light) verdict is still one walk of the same
     // ray, so the mask, and every colour, is the one the owner alone would have made.
-    constexpr bool kPair = kInLane && !kSteal && (kAnyHit || RT_PAIR_CLOSEST);
+    constexpr bool kPair = kInLane && !kSteal;   // (the closest-hit-shadow instantiations too: scenes with transparency)
     Secondary none;
     none.state = kChildNone;
     none.local = mk(0, 0, 0);   // trace() miss: black (:389-391)
     int bidx = -1;
     V3 bI = mk(0, 0, 0);
     V3 ray = sub(dst, org);
-    if (RT_LDS_PARK && park.base) {
-        park.put(0, ray.x); park.put(1, ray.y); park.put(2, ray.z);
-        park.put(3, as_float(lvl)); park.put(4, as_float(sample));
-    }
     bvh_query_w<false, W, kSteal>(sc, org, ray, live, bidx, bI, stack, wc.tests, wc.visits);
     if (bidx >= sc.nt) { w.counters[kErrorSlot] = 1; bidx = -1; }
     const bool hit = live && bidx >= 0;
@@ -2214,11 +2002,6 @@ __device__ __forceinline__ Secondary chain_step(const DevScene &sc, const ShadeP
         }
     }
     if (!hit) return none;   // (a helper's or an idle lane's return value is not used)
-    if (RT_LDS_PARK && park.base) {
-        ray = mk(park.get(0), park.get(1), park.get(2));
-        lvl = as_int(park.get(3));
-        sample = as_int(park.get(4));
-    }
     return shade_hit<kInLane, false>(sc, p, w, step, sample, ray, lvl, bidx, bI, [&](int l) { return ((mask >> l) & 1u) != 0; });
 }
 
@@ -2342,7 +2125,7 @@ __device__ __forceinline__ void quad_batch(const DevScene &sc, const ShadeParams
 }
 
 // k_chain's explicit arguments as laid out in the kernel-argument segment (in order, each at its
-// natural alignment, as the members of a struct), for RT_OPAQUE_ARGS. The layout is a property of
+// natural alignment, as the members of a struct), for the opaque-argument reads. The layout is a property of
 // the kernel's signature, so it is checked once per kernel instantiation rather than per launch:
 // probe_chain_kernargs launches k_chain_kernarg_probe, a kernel with k_chain's exact parameter list,
 // which compares every argument with the ChainKernargs member at its place (chain_kernarg_mismatch)
@@ -2366,7 +2149,7 @@ struct ChainKernargs {
     FrameSet fs;
 };
 // the kernel-argument segment is at most 4 KB (the scene, the shading parameters with 16 lights, the
-// workspace, the frame geometry and the multi-frame set are 2,032 B now): growth past it fails here
+// workspace, the frame geometry and the multi-frame set are 2,024 B now): growth past it fails here
 static_assert(sizeof(ChainKernargs) <= 4096, "k_chain's arguments exceed the 4 KB kernel-argument segment");
 
 // Bit k set: argument k of k_chain is not where ChainKernargs places it. The probe launch fills each
@@ -2411,14 +2194,7 @@ __global__ __launch_bounds__(kBvhBlock) __attribute__((amdgpu_waves_per_eu(kStea
     float *__restrict__ out_f32, int fuse_spp, int spb, int nbatch, const FrameGeom g, int split, int split8, const FrameSet fs) {
     extern __shared__ int32_t lds_stack[];
     __shared__ int s_q[kChainSteps], s_sh[kChainSteps];
-#if RT_LDS_PARK
-    __shared__ float s_park[kParkWords * kBvhBlock];
-    const Park park{s_park};
-#else
-    const Park park{nullptr};
-#endif
     for (int i = threadIdx.x; i < kChainSteps; i += kBvhBlock) { s_q[i] = 0; s_sh[i] = 0; }
-#if RT_OPAQUE_ARGS
     {   // a per-launch spot check of six fields besides the load-time probe (k_chain_kernarg_probe checks
         // every word): a mismatch sets the error slot and ends the launch. (A NaN corner is not one.
         // Without this block the compiler allocates the kernel's registers differently: 28 instead of
@@ -2431,7 +2207,6 @@ __global__ __launch_bounds__(kBvhBlock) __attribute__((amdgpu_waves_per_eu(kStea
             return;
         }
     }
-#endif
     __syncthreads();
     const LaneStack stack = lane_stack(sc, lds_stack);
     WorkTally<kCount> wc, ws;   // closest-hit and shadow work (totals only: lanes diverge here)
@@ -2456,7 +2231,6 @@ __global__ __launch_bounds__(kBvhBlock) __attribute__((amdgpu_waves_per_eu(kStea
     const int nfr = (kInLane && kMulti) ? max(1, fs.count) : 1;
     drive_queries((nbatch + extra) * kWave * nfr, dyn ? 4 : (sc.chain_split & 3), dyn ? &w.counters[kWaveQueueSlot] : w.wq + (2 * first) * kWqSlot,
                   [&](int j0, int vend) {
-#if RT_OPAQUE_ARGS
         // the frame geometry, shading parameters, scene and workspace are read from the kernel
         // arguments through a pointer the compiler cannot follow across batches, so their scalar
         // loads stay in the batch loop instead of being hoisted to the kernel's start and held
@@ -2468,19 +2242,6 @@ __global__ __launch_bounds__(kBvhBlock) __attribute__((amdgpu_waves_per_eu(kStea
         const ShadeParams &pl = *(const ShadeParams *)&ka->p;
         const DevScene &scb = *(const DevScene *)&ka->sc;
         const DevWork &wb = *(const DevWork *)&ka->w;
-#if RT_OPAQUE_ARGS >= 2
-        uint8_t *const out_u8 = ka->out_u8;
-        float *const out_f32 = ka->out_f32;
-        const int first = ka->first, ordered = ka->ordered, fuse_spp = kInLane ? ka->fuse_spp : 0, spb = kInLane ? ka->spb : kWave;
-        const int split8 = ka->split8, s2 = ka->split & 0xFFFF, s4 = ka->split >> 16, extra = 7 * split8 + 3 * s4 + s2;
-        const int spp = kInLane ? fuse_spp : 1, ppb = spb / spp;
-#endif
-#else
-        const FrameGeom &gl = g;
-        const ShadeParams &pl = p;
-        const DevScene &scb = sc;
-        const DevWork &wb = w;
-#endif
         // this wave's virtual batch: wave-uniform in every distribution (xcd_segment hands out whole
         // 64-query chunks), so it and everything derived from it (frame, batch, split tier, part, the
         // order's entry) live in scalar registers
@@ -2488,17 +2249,12 @@ __global__ __launch_bounds__(kBvhBlock) __attribute__((amdgpu_waves_per_eu(kStea
         const int fr = nfr > 1 ? vball % nfr : 0, vb = nfr > 1 ? vball / nfr : vball;   // (its frame, its batch in it)
         // the frame's outputs, read where they are written (held from the batch's start, they stayed live
         // through the chain and spilled), and its corner rays
-#if RT_OPAQUE_ARGS
         auto frame_out = [&](auto which) {
             KargPtr kb = (KargPtr)__builtin_amdgcn_kernarg_segment_ptr();
             asm volatile("" : "+s"(kb));
             return which(nfr > 1, kb->fs.out_u8[fr], kb->fs.out_f32[fr], kb->out_u8, kb->out_f32);
         };
         const float(*const fcs)[3] = (const float(*)[3]) & ka->fs.corners[fr][0];
-#else
-        auto frame_out = [&](auto which) { return which(nfr > 1, fs.out_u8[fr], fs.out_f32[fr], out_u8, out_f32); };
-        const float(*const fcs)[3] = fs.corners[fr];
-#endif
         auto o8f = [&]() { return frame_out([](bool m, uint8_t *a, float *, uint8_t *c, float *) { return m ? a : c; }); };
         auto of32f = [&]() { return frame_out([](bool m, uint8_t *, float *b, uint8_t *, float *d) { return m ? b : d; }); };
         // split tiers of the order: 8 parts, then 4, then 2; part = which part of batch order[ob]
@@ -2538,7 +2294,7 @@ __global__ __launch_bounds__(kBvhBlock) __attribute__((amdgpu_waves_per_eu(kStea
                 quad_batch<kAnyHit, kCount>(scb, pl, wb, gl, nfr > 1 ? fcs : gl.corners, lds_stack, s_q, s_sh, wc, ws, o8f(), of32f(),
                                             fuse_spp, pb * spb + part * plen, min(plen, spb - part * plen), nq);
         } else {
-        constexpr bool kPair = kInLane && !kSteal && (kAnyHit || RT_PAIR_CLOSEST);   // (every lane stays in the step loop, chain_step)
+        constexpr bool kPair = kInLane && !kSteal;   // (every lane stays in the step loop, chain_step)
         const bool pair = kPair && scb.shadow_helpers && (pl.flags & RT_SHADOWS) && pl.n_lights > 1;
         [&]() {
         bool own = lane_on && j < nq;
@@ -2577,7 +2333,7 @@ __global__ __launch_bounds__(kBvhBlock) __attribute__((amdgpu_waves_per_eu(kStea
             if (kPair && !__any(live)) break;
             if (live && step > first) atomicAdd(&s_q[step], 1);
             const Secondary sec = chain_step<kAnyHit, W, kCount, kInLane, kSteal>(scb, pl, wb, step, sample, org, dst, lvl, stack,
-                                                                                  s_sh, wc, ws, live, pair, park);
+                                                                                  s_sh, wc, ws, live, pair);
             if (!live) continue;
             if (sec.state != kChildTrace) {
                 if (kInLane)   // the chain ends here: fold it in the lane (fold_chain's arithmetic)
@@ -2600,11 +2356,9 @@ __global__ __launch_bounds__(kBvhBlock) __attribute__((amdgpu_waves_per_eu(kStea
         } else if (kInLane) {   // k_frame's arithmetic: a pixel's fuse_spp sub-samples sit in adjacent lanes
             // (the pixel's first lane and the divisor made here from the argument, not at the kernel's start:
             // held across the batch they were spilled to scratch and reloaded per batch)
-#if RT_OPAQUE_ARGS
             KargPtr kf = (KargPtr)__builtin_amdgcn_kernarg_segment_ptr();
             asm volatile("" : "+s"(kf));
             const int fuse_spp = kf->fuse_spp;
-#endif
             const int pix_lane = (fuse_spp & (fuse_spp - 1)) == 0 ? (lane & ~(fuse_spp - 1)) : lane - lane % fuse_spp;
             V3 acc = mk(0, 0, 0);
             for (int sub = 0; sub < fuse_spp; ++sub)   // summed in sub-sample order (main.cpp:377-391)
@@ -2804,31 +2558,10 @@ __global__ __launch_bounds__(kBlock) void k_face_normals(const float *__restrict
     normals[i] = make_float4(n.x, n.y, n.z, 0.0f);
 }
 
-// shade() normalises the hit's normal in place once per diffuse and once per specular term of every lit
-// light (diffuseOnly / blinnPhongSpecularOnly, raytracing.cpp:199,213): the k-th state of a face's normal
-// is N^k(n). Where N(N(N(n))) == N(n) bit for bit (the states alternate from the first on: nearly every
-// face), the two states are tabled once here with the kernels' own normalize, and shading picks state k
-// by its parity instead of normalising again (w = 1 marks the face; otherwise shading normalises).
-__global__ __launch_bounds__(kBlock) void k_normal_table(float4 *__restrict__ normals, float4 *__restrict__ ntab, int32_t nt) {
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-    if (i >= nt) return;
-    const float4 n0 = normals[i];
-    V3 n1 = mk(n0.x, n0.y, n0.z);
-    normalize(n1);
-    V3 n2 = n1;
-    normalize(n2);
-    V3 n3 = n2;
-    normalize(n3);
-    const bool ok = as_int(n3.x) == as_int(n1.x) && as_int(n3.y) == as_int(n1.y) && as_int(n3.z) == as_int(n1.z);
-    ntab[2 * i] = make_float4(n1.x, n1.y, n1.z, 0.0f);
-    ntab[2 * i + 1] = make_float4(n2.x, n2.y, n2.z, 0.0f);
-    normals[i] = make_float4(n0.x, n0.y, n0.z, ok ? 1.0f : 0.0f);
-}
-
 // ---- dynamic geometry: refit (rt_scene_update_vertices; argument in bvh.cpp) ----------------------
 // Everything below restates host code operation for operation (no contraction; f64 '/', sqrt and the
 // f64 -> f32 conversion are IEEE on gfx950), so a refitted device scene holds the bytes a fresh scene's
-// upload would: build_tri_records (scene_loader.cpp), k_face_normals + k_normal_table above, and
+// upload would: build_tri_records (scene_loader.cpp), k_face_normals above, and
 // acceptance_box / down / up / build_bvh's scene_m1 (bvh.cpp). std::min / std::max are spelled out as the
 // compares they are.
 __device__ __forceinline__ double min_std(double a, double b) { return (b < a) ? b : a; }
@@ -2888,7 +2621,7 @@ __device__ int refit_class(const float n[3], float uu_f, float vv_f, float D_f, 
 }
 
 // One lane per triangle (and per vertex, for scene_m1): the triangle's record into d_tris and into its
-// leaf or always slot, its face normal and normal table, its padded acceptance box into its leaf slot's
+// leaf or always slot, its face normal, its padded acceptance box into its leaf slot's
 // box, and its class against the class it was built with (a.tri_slot; null: no tree, records and normals
 // only). Nothing here is read by the same launch: the traversal kernels fetch the records in later ones.
 __global__ __launch_bounds__(kBlock) void k_refit_tris(const RefitArgs a) {
@@ -2914,29 +2647,13 @@ __global__ __launch_bounds__(kBlock) void k_refit_tris(const RefitArgs a) {
     const V3 n = mk(u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x);   // :108
     const float uu = dot(u, u), uv = dot(u, v), vv = dot(v, v);                    // :134-136
     const float D = uv * uv - uu * vv;                                             // :140
-    float dslot = D;
-    if (RT_TRI_RCP) {   // tri_rcp_slot (rt_internal.h)
-        const float ad = fabsf(D);
-        const int ex = (as_int(D) >> 23) & 0xff;
-        dslot = (ex != 0 && ex != 0xff && ad >= 0x1p-30f && ad <= 0x1p30f) ? 1.0f / D : as_float(0x7fc00000);
-    }
     const float4 q0 = make_float4(p0.x, p0.y, p0.z, uu), q1 = make_float4(u.x, u.y, u.z, uv);
-    const float4 q2 = make_float4(v.x, v.y, v.z, vv), q3 = make_float4(n.x, n.y, n.z, dslot);
+    const float4 q2 = make_float4(v.x, v.y, v.z, vv), q3 = make_float4(n.x, n.y, n.z, D);
     float4 *t = reinterpret_cast<float4 *>(a.tris + i);
     t[0] = q0; t[1] = q1; t[2] = q2; t[3] = q3;
-    // k_face_normals and k_normal_table
-    V3 n0 = n;
+    V3 n0 = n;   // k_face_normals
     normalize(n0);
-    V3 n1 = n0;
-    normalize(n1);
-    V3 n2 = n1;
-    normalize(n2);
-    V3 n3 = n2;
-    normalize(n3);
-    const bool ok = as_int(n3.x) == as_int(n1.x) && as_int(n3.y) == as_int(n1.y) && as_int(n3.z) == as_int(n1.z);
-    a.ntab[2 * i] = make_float4(n1.x, n1.y, n1.z, 0.0f);
-    a.ntab[2 * i + 1] = make_float4(n2.x, n2.y, n2.z, 0.0f);
-    a.normals[i] = make_float4(n0.x, n0.y, n0.z, ok ? 1.0f : 0.0f);
+    a.normals[i] = make_float4(n0.x, n0.y, n0.z, 0.0f);
     if (!a.tri_slot) return;
     const float nn[3] = {n.x, n.y, n.z};
     float lo[3], hi[3];
@@ -4016,9 +3733,6 @@ __global__ __launch_bounds__(kBlock) void k_assemble_pieces(const uint8_t *__res
 // frame's tile row, reads each from its rank's shard (768 contiguous bytes) into LDS and writes the 16
 // frame rows they cover as runs of kAsmTiles x 48 contiguous bytes. (k_assemble_pieces reads tile rows
 // in order but writes them as 48-byte pieces 5,760 bytes apart; here no store is narrower than a run.)
-#ifndef RT_ASM_ROWS
-#define RT_ASM_ROWS 1   // 0: every un-permute through k_assemble_pieces (A/B)
-#endif
 constexpr int kAsmTiles = 16;
 constexpr int kAsmTileBytes = 16 * 16 * 3;          // 768
 constexpr int kAsmLdsStride = kAsmTileBytes + 48;   // (a pad that spreads a row's three tile reads over banks)
@@ -4060,7 +3774,6 @@ inline unsigned grid_for(int64_t n) { return static_cast<unsigned>((n + kBlock -
 
 }  // namespace
 
-bool tri_rcp_records() { return RT_TRI_RCP != 0; }   // the records' D slot holds rD (test_triangle)
 
 // The geometry's divisors as multiply-high magic numbers (fastdiv.h), for the kernels' index decoding.
 static FrameGeom with_divisors(FrameGeom g) {
@@ -4451,11 +4164,6 @@ void launch_gen_rays_device(const void *org, const void *dst, int32_t ray_stride
     else hipLaunchKernelGGL(k_gen_rays_device<3>, dim3(grid_for(n)), dim3(kBlock), 0, stream, org, dst, n, w);
 }
 
-void launch_normal_table(float4 *normals, float4 *ntab, int32_t nt, hipStream_t stream) {
-    if (nt <= 0) return;
-    hipLaunchKernelGGL(k_normal_table, dim3(grid_for(nt)), dim3(kBlock), 0, stream, normals, ntab, nt);
-}
-
 void launch_face_normals(const float *xyz, const uint32_t *tri_v, int32_t nt, float4 *normals, hipStream_t stream) {
     if (nt <= 0) return;
     hipLaunchKernelGGL(k_face_normals, dim3(grid_for(nt)), dim3(kBlock), 0, stream, xyz, tri_v, nt, normals);
@@ -4607,7 +4315,7 @@ void launch_assemble_tiles(const uint8_t *gathered, int32_t width, int32_t heigh
     const int64_t ppr = (static_cast<int64_t>(tw) * 3 + 15) / 16, npieces = rows * ppr;
     const int32_t tiles_y = tiles_total / tiles_x;
     const int64_t chunks = (tiles_x + kAsmTiles - 1) / kAsmTiles, blocks = static_cast<int64_t>(frames) * tiles_y * chunks;
-    if (RT_ASM_ROWS && tw == 16 && th == 16 && width % 16 == 0 && slot0 == 0 && nslots == slots &&
+    if (tw == 16 && th == 16 && width % 16 == 0 && slot0 == 0 && nslots == slots &&
         ((reinterpret_cast<uintptr_t>(gathered) | reinterpret_cast<uintptr_t>(out)) & 15) == 0 &&
         static_cast<int64_t>(frames) * tiles_total < (int64_t(1) << 32) && blocks < (int64_t(1) << 31)) {
         const AssembleRowDivs dv{make_udiv(static_cast<uint32_t>(nranks)), make_udiv(static_cast<uint32_t>(chunks)),

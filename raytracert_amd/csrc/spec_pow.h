@@ -8,14 +8,6 @@
 #define RT_SPEC_POW_H_
 
 #include <cmath>
-#include <cstdint>
-#include <cstring>
-
-#include "spec_pow_tab.h"
-
-#ifndef RT_SPEC_POW_TABLE
-#define RT_SPEC_POW_TABLE 0   // 1: table-driven log2/exp2 (r05, measured 1-2% slower: profiles/r05zh_ab_spec_table.txt)
-#endif
 
 #if defined(__HIP__)
 #define RT_HD __host__ __device__
@@ -51,34 +43,6 @@ RT_HD inline float spec_pow(float xf, float yf) {
     if (xf == 1.0f) return sgn;
     const double y = static_cast<double>(yf);
     if (xf == 0.0f) return sgn * (y > 0 ? 0.0f : INFINITY);
-#if RT_SPEC_POW_TABLE
-    // Table-driven (r05): log2(x) = e + logc + log1p(r) / ln 2 with m = x 2^-e in [1, 2), r = m invc - 1
-    // (one fma, |r| <= 2^-7, degree 7: truncation < 3e-17); exp2(t) = 2^n T[j] e^u, t = n + j/64 + g,
-    // u = g ln 2, |u| <= 0.0055, degree 5 (truncation < 4e-17). About half the double instructions of
-    // the atanh / degree-14 form below, and no double division; ~1e-15 relative before the float rounding.
-    int e;
-    const float mf = std::frexp(xf, &e) * 2.0f;                        // [1, 2), exact
-    e -= 1;
-    uint32_t mb;
-    std::memcpy(&mb, &mf, sizeof(mb));
-    const int i = static_cast<int>((mb >> 17) & 63u);
-    const double r = std::fma(static_cast<double>(mf), kSpecLogTab[i][0], -1.0);
-    double p = sconst(1.0 / 7);
-    p = std::fma(p, r, sconst(-1.0 / 6)); p = std::fma(p, r, sconst(1.0 / 5)); p = std::fma(p, r, sconst(-1.0 / 4));
-    p = std::fma(p, r, sconst(1.0 / 3));  p = std::fma(p, r, -0.5);            p = std::fma(p, r, 1.0);
-    double t = y * std::fma(p * r, sconst(1.4426950408889634074), static_cast<double>(e) + kSpecLogTab[i][1]);
-    if (t != t) return NAN;   // (not reached: NaN inputs returned above)
-    if (t < -1100.0) t = -1100.0;                                     // 0 after rounding either way
-    if (t > 1100.0) t = 1100.0;                                       // inf
-    const double k = std::rint(t * 64.0);
-    const int ki = static_cast<int>(k);
-    const double u = (t - k * (1.0 / 64)) * sconst(0.69314718055994530942);   // t - k/64 exact
-    double q = sconst(1.0 / 120);
-    q = std::fma(q, u, sconst(1.0 / 24)); q = std::fma(q, u, sconst(1.0 / 6)); q = std::fma(q, u, 0.5);
-    q = std::fma(q, u, 1.0);
-    q = std::fma(q * u, kSpecExpTab[ki & 63], kSpecExpTab[ki & 63]);          // T (1 + u q)
-    return sgn * static_cast<float>(std::ldexp(q, ki >> 6));          // (arithmetic shift: floor(k / 64))
-#else
     // log2(x) = e + ln(m) / ln 2, m in [sqrt(1/2), sqrt(2)), ln(m) = 2 atanh(s), s = (m-1)/(m+1)
     int e;
     double m = std::frexp(static_cast<double>(xf), &e);
@@ -106,7 +70,6 @@ RT_HD inline float spec_pow(float xf, float yf) {
     q = std::fma(q, g, sconst(1.0 / 6.0));          q = std::fma(q, g, 0.5);
     q = std::fma(q, g, 1.0);                q = std::fma(q, g, 1.0);
     return sgn * static_cast<float>(std::ldexp(q, static_cast<int>(n)));
-#endif
 }
 
 }  // namespace rt

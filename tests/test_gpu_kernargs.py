@@ -1,6 +1,6 @@
 """The chain kernel's kernel-argument view (RT_OPAQUE_ARGS, VERDICT r04 "weak" 9).
 
-k_chain reads its 508 argument words, 2,032 B (the FrameSet of a multi-frame launch, ~904 B, and the lights' normalised
+k_chain reads its 506 argument words, 2,024 B (the FrameSet of a multi-frame launch, ~904 B, and the lights' normalised
 positions, 192 B, since r05) through a struct view of the kernel-argument segment
 (ChainKernargs). At scene upload the library runs k_chain_kernarg_probe once per device: a kernel
 with k_chain's parameter list (a static_assert pins the two signatures together) that compares

@@ -88,7 +88,7 @@ def test_refit_frames_and_queries_equal_fresh_and_oracle(arr, d003):
             assert np.array_equal(_bits(pts[i]), _bits(oI)), i
             hits_sliver += oi == 1640
         assert hits_sliver > 0 and (idx >= 0).sum() > 50
-        # one chain of trace() calls: normals, the normal table, shadow rays
+        # one chain of trace() calls: normals, shadow rays
         k = int(np.argmax(idx[20:] >= 0)) + 20
         gb, grgb = sc.debug_trace(P, o[k], d[k])
         ob, _ = d003["oracle"].debug_trace(_op(), o[k], d[k])
