@@ -19,7 +19,10 @@
  *   rt_intersect_mesh_device  intersectMesh, rays and results in device memory   raytracing.cpp:161-192
  *   rt_occluded_device    isShadow's verdict for given rays, in device memory  raytracing.cpp:249-258
  *   rt_trace_rays_device  performRayTracing, rays and colours in device memory raytracing.cpp:410-416
- *   rt_debug_trace        debug key 'd' (shoot + trace)     raytracing.cpp:493-510
+ *   rt_closest_hit_range_device  (an extension: the closest hit within a per-ray distance range, with its
+ *                         distance and the reference's s, t; raytracing.cpp:106-149, :182)
+ *   rt_occluded_range_device  (an extension: occlusion within a range, isShadow's rule or any opaque triangle)
+ *   rt_debug_trace       debug key 'd' (shoot + trace)     raytracing.cpp:493-510
  *                         (batched; also trace(o,d,lvl) at lvl 0, raytracing.h:30)
  *   rt_render_tile        the 'r'-key frame loop            main.cpp:340-411 (loop :355-395,
  *                         + RGBValue clamp :24-42 + Image::writeImage quantisation :102-128)
@@ -305,6 +308,43 @@ int rt_intersect_mesh_device(rt_scene *scene, const void *d_origins, const void 
  * origin it wants. Returns after enqueueing; uses no render workspace. */
 int rt_occluded_device(rt_scene *scene, const void *d_origins, const void *d_dests, int32_t ray_stride,
                        int32_t n, const void *d_count, void *d_blocked_out, void *stream);
+/* Ranged device queries (extensions): the two queries above restricted to a per-ray distance range, with a
+ * hit record in place of the bare index. Everything is decided in binary32.
+ * A triangle is ACCEPTED by ray i exactly when rayIntersectTriangle accepts it (raytracing.cpp:106-149), and
+ * its distance is the float intersectMesh compares (:182). It is IN RANGE iff tmin_i <= distance < tmax_i, with
+ *   tmin_i = d_tmin ? d_tmin[i] : 0
+ *   tmax_i = d_tmax ? d_tmax[i] : (flags & RT_RANGE_TO_DEST) ? |dest - origin| : +inf
+ * (|dest - origin| = sqrtf((dx*dx + dy*dy) + dz*dz), the reference's Vec3D length), both clamped above to
+ * FLT_MAX as intersectMesh's own bound is. With d_tmax given RT_RANGE_TO_DEST has no effect. A NaN bound,
+ * tmax <= 0 or tmin >= tmax is an empty range: a miss. d_tmin / d_tmax are n device floats each (4-byte
+ * aligned) or NULL; rows at or past the live count are not read.
+ * Rays, ray_stride, d_count, stream, ordering against updates, and the errors are those of the entries above;
+ * in addition RT_E_ARG for d_hit_out not 16-byte aligned, d_tmin / d_tmax not 4-byte aligned, an unknown
+ * flag bit, or a flag the entry does not use. Outputs must not overlap the rays, the bounds or d_count. */
+typedef struct {
+    int32_t triangle;   /* the closest in-range accepted triangle, or -1 */
+    float distance;     /* its distance (raytracing.cpp:182), +inf on a miss */
+    float s, t;         /* the reference's parametric coordinates of the hit (:144, :148): the point is
+                           V0 + s (V1 - V0) + t (V2 - V0); 0, 0 on a miss */
+} rt_hit;               /* 16 bytes */
+#define RT_RANGE_TO_DEST      (1u << 0)   /* tmax defaults to the ray's own length: the segment origin..dest */
+#define RT_OCCLUDE_ANY_OPAQUE (1u << 1)   /* rt_occluded_range_device: any non-transparent triangle in range blocks */
+/* d_hit_out[i] (n x rt_hit, 16-byte aligned) = the lexicographic (distance, index) minimum over the in-range
+ * accepted triangles, or {-1, +inf, 0, 0}; d_point_out (3n packed floats, may be NULL) = the intersection
+ * point (:130) or (0,0,0). With both bounds NULL and flags 0, triangle and point are rt_intersect_mesh_device's
+ * bits. tmin = nextafterf(previous distance, +inf) steps to the next surface along the ray.
+ * flags: RT_RANGE_TO_DEST. */
+int rt_closest_hit_range_device(rt_scene *scene, const void *d_origins, const void *d_dests, int32_t ray_stride,
+                                int32_t n, const void *d_count, const void *d_tmin, const void *d_tmax, uint32_t flags,
+                                void *d_hit_out, void *d_point_out, void *stream);
+/* d_blocked_out[i] (n x uint8): by default isShadow's rule inside the range, 1 when the closest in-range
+ * accepted triangle exists and its material is not transparent; with RT_OCCLUDE_ANY_OPAQUE, 1 when SOME
+ * in-range accepted triangle's material is not transparent (line of sight: glass in front of a wall does not
+ * hide the wall). With RT_RANGE_TO_DEST this answers "are origin and dest mutually visible".
+ * flags: RT_RANGE_TO_DEST, RT_OCCLUDE_ANY_OPAQUE. */
+int rt_occluded_range_device(rt_scene *scene, const void *d_origins, const void *d_dests, int32_t ray_stride,
+                             int32_t n, const void *d_count, const void *d_tmin, const void *d_tmax, uint32_t flags,
+                             void *d_blocked_out, void *stream);
 /* performRayTracing (raytracing.cpp:410-416) for rays in device memory: d_rgb_out[3*i..] (3n packed floats),
  * bit for bit rt_trace_rays' rgb_out. counts as in rt_trace_rays; non-NULL synchronises the stream. Uses
  * render pipeline 0's workspace (ordered against the frames that use it): returns after enqueueing when

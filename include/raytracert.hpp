@@ -193,6 +193,20 @@ class RayTracer {
                          void *d_blocked_out, void *stream) {
         check(rt_occluded_device(scene_, d_origins, d_dests, ray_stride, n, d_count, d_blocked_out, stream));
     }
+    // ... and within a per-ray distance range [tmin, tmax) (rt_closest_hit_range_device, rt_occluded_range_device:
+    // d_tmin / d_tmax n device floats each or null, flags RT_RANGE_TO_DEST / RT_OCCLUDE_ANY_OPAQUE; d_hit_out
+    // n x rt_hit, d_point_out may be null)
+    void closest_hit_range_device(const void *d_origins, const void *d_dests, int32_t ray_stride, int32_t n, const void *d_count,
+                                  const void *d_tmin, const void *d_tmax, uint32_t flags, void *d_hit_out, void *d_point_out,
+                                  void *stream) {
+        check(rt_closest_hit_range_device(scene_, d_origins, d_dests, ray_stride, n, d_count, d_tmin, d_tmax, flags, d_hit_out,
+                                          d_point_out, stream));
+    }
+    void occluded_range_device(const void *d_origins, const void *d_dests, int32_t ray_stride, int32_t n, const void *d_count,
+                               const void *d_tmin, const void *d_tmax, uint32_t flags, void *d_blocked_out, void *stream) {
+        check(rt_occluded_range_device(scene_, d_origins, d_dests, ray_stride, n, d_count, d_tmin, d_tmax, flags, d_blocked_out,
+                                       stream));
+    }
     void perform_ray_tracing_device(const void *d_origins, const void *d_dests, int32_t ray_stride, int32_t n, void *d_rgb_out,
                                     void *stream, uint64_t counts[3] = nullptr) {
         rt_params p = params();

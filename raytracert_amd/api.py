@@ -418,6 +418,65 @@ class Scene:
                                        C.c_void_p(blocked.data_ptr()), self._stream_ptr(stream)))
         return blocked[:n]
 
+    def _device_bound(self, name: str, what: str, t, n: int):
+        """A ranged query's tmin / tmax: None, or a contiguous CUDA float32 tensor of n (or more) elements."""
+        import torch
+        if t is None:
+            return None
+        if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != self.device or t.dtype != torch.float32
+                or t.dim() != 1 or not t.is_contiguous() or t.shape[0] < n):
+            raise ValueError(f"{name}: {what} must be a contiguous CUDA float32 tensor of shape (>= {n},) on the scene's device")
+        return C.c_void_p(t.data_ptr())
+
+    def closest_hit_device(self, origins, dests, tmin=None, tmax=None, to_dest: bool = False, count=None, out=None,
+                           want_points: bool = False, stream=None):
+        """rt_closest_hit_range_device: per ray, the closest accepted triangle whose distance lies in [tmin, tmax),
+        with that distance and the reference's s, t of the hit. Rays, count and stream as intersect_mesh_device.
+        tmin / tmax: optional CUDA float32 tensors of n elements (defaults 0 and +inf; with to_dest and no tmax,
+        the ray's own length, so only hits between origin and dest count). A NaN bound, tmax <= 0 or tmin >= tmax
+        is an empty range: a miss. Returns (triangle[n] int32, distance[n] float32, st[n, 2] float32), views of
+        one (n, 4) int32 record tensor (rt_hit: a miss is -1, +inf, 0, 0), and with want_points also point[n, 3].
+        out: that (>= n, 4) int32 record tensor to write into, or with want_points a (records, points) pair.
+        With tmin = tmax = None and to_dest False, triangle and point are intersect_mesh_device's bits;
+        tmin = torch.nextafter(distance, inf) steps each ray to its next surface."""
+        import torch
+        name = "closest_hit_device"
+        n, stride = self._device_rays(name, "intersect_mesh", origins, dests)
+        cnt = self._device_count(name, count)
+        lo, hi = self._device_bound(name, "tmin", tmin, n), self._device_bound(name, "tmax", tmax, n)
+        if want_points and out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
+            raise ValueError(f"{name}: with want_points, out must be a (records, points) pair")
+        out_rec = out[0] if (want_points and out is not None) else out
+        rec = self._device_out(name, out_rec, n, torch.int32, (4,), 0, False)
+        if out_rec is None and count is not None:      # entries a device count leaves unwritten: the miss record
+            rec[:, 0], rec[:, 1], rec[:, 2:] = -1, 0x7F800000, 0      # (device fills: no host copy)
+        if rec.data_ptr() % _capi.HIT_BYTES:
+            raise ValueError(f"{name}: the record tensor must be 16-byte aligned")
+        pts = self._device_out(name, None if out is None else out[1], n, torch.float32, (3,), 0.0, count is not None) if want_points else None
+        check(lib().rt_closest_hit_range_device(self._h, C.c_void_p(origins.data_ptr()), C.c_void_p(dests.data_ptr()), stride, n, cnt,
+                                                lo, hi, _capi.RANGE_TO_DEST if to_dest else 0, C.c_void_p(rec.data_ptr()),
+                                                None if pts is None else C.c_void_p(pts.data_ptr()), self._stream_ptr(stream)))
+        f = rec[:n].view(torch.float32)
+        res = (rec[:n, 0], f[:, 1], f[:, 2:4])
+        return res + (pts[:n],) if want_points else res
+
+    def occluded_range_device(self, origins, dests, tmin=None, tmax=None, to_dest: bool = False, any_opaque: bool = False,
+                              count=None, out=None, stream=None):
+        """rt_occluded_range_device: occlusion inside [tmin, tmax) (bounds and to_dest as closest_hit_device).
+        Returns blocked[n] uint8. By default isShadow's rule within the range: 1 when the closest in-range hit
+        exists and its material is not transparent. any_opaque: 1 when some in-range accepted triangle's material
+        is not transparent. With to_dest: whether origin and dest cannot see each other."""
+        import torch
+        name = "occluded_range_device"
+        n, stride = self._device_rays(name, "intersect_mesh", origins, dests)
+        cnt = self._device_count(name, count)
+        lo, hi = self._device_bound(name, "tmin", tmin, n), self._device_bound(name, "tmax", tmax, n)
+        blocked = self._device_out(name, out, n, torch.uint8, (), 0, count is not None)
+        flags = (_capi.RANGE_TO_DEST if to_dest else 0) | (_capi.OCCLUDE_ANY_OPAQUE if any_opaque else 0)
+        check(lib().rt_occluded_range_device(self._h, C.c_void_p(origins.data_ptr()), C.c_void_p(dests.data_ptr()), stride, n, cnt,
+                                             lo, hi, flags, C.c_void_p(blocked.data_ptr()), self._stream_ptr(stream)))
+        return blocked[:n]
+
     def perform_ray_tracing_device(self, params: RenderParams, origins, dests, out=None, stream=None, want_counts: bool = False):
         """rt_trace_rays_device: performRayTracing for rays born on the GPU (arguments as
         intersect_mesh_device, without count). Returns rgb[n, 3] float32 (unclamped, perform_ray_tracing's

@@ -209,6 +209,14 @@ void launch_intersect_only(const DevScene &s, const float4 *org, const float4 *d
 // material in use, else closest hit and its material's test). The other outputs may be null.
 void launch_query_rays(const DevScene &s, bool occluded, const void *org, const void *dst, int32_t ray_stride, int32_t n,
                        const int32_t *d_count, int32_t *idx, float *point, uint8_t *blocked, hipStream_t stream);
+// Ranged device queries (rt_closest_hit_range_device / rt_occluded_range_device): launch_query_rays with a
+// per-ray range [tmin, tmax) (d_tmin / d_tmax: n floats each or null; to_dest: without d_tmax, tmax is the
+// ray's own length). !occluded: hit[n] 16-byte records {triangle, distance, s, t} and, when point is not
+// null, point[3 n]. occluded: blocked[n] bytes; any_opaque: "some in-range accepted triangle is not
+// transparent" instead of isShadow's rule on the closest one.
+void launch_range_rays(const DevScene &s, bool occluded, bool any_opaque, bool to_dest, const void *org, const void *dst,
+                       int32_t ray_stride, int32_t n, const int32_t *d_count, const float *d_tmin, const float *d_tmax, void *hit,
+                       float *point, uint8_t *blocked, hipStream_t stream);
 // launch_gen_rays from the caller's device arrays in either layout (rt_trace_rays_device)
 void launch_gen_rays_device(const void *org, const void *dst, int32_t ray_stride, int32_t n, const DevWork &w,
                             hipStream_t stream);

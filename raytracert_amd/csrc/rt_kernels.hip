@@ -158,9 +158,20 @@ __device__ __forceinline__ void sgpr_fence(const TriRec &T) {
 // distance), so the work a launch performed is counted, not a union path every test is assumed to take.
 constexpr int kTestStages = 5;
 constexpr int kTestStageFlops[kTestStages] = {14, 1, 23, 5, 9};
-template <bool kAnyHit, bool kLex = false, bool kSignFirst = false, bool kStages = false>
+// kRange (the ranged device queries, rt_closest_hit_range_device / rt_occluded_range_device): a triangle
+// counts only when tmin <= dist < tmax. The walks start best at tmax, so the strict '<' of the update is
+// the upper bound; the lower one is the test below, made once the distance is known. kRangeOpaque (any-hit
+// only): the material is looked up once a triangle is accepted and in range, and a transparent one is
+// passed over (it does not end the walk). kRangeNone is every walk there was before: rg is never read.
+enum : int { kRangeNone = 0, kRangeBounded = 1, kRangeOpaque = 2 };
+struct RayRange {
+    float tmin = 0.0f, tmax = FLT_MAX;
+    const uint32_t *tri_mat = nullptr;      // kRangeOpaque only
+    const DevMaterial *mats = nullptr;
+};
+template <bool kAnyHit, bool kLex = false, bool kSignFirst = false, bool kStages = false, int kRange = kRangeNone>
 __device__ __forceinline__ void test_triangle(const TriRec &T, int t, V3 o, V3 dir, float &best, int &bidx, V3 &bI,
-                                              bool &done, unsigned *stg = nullptr) {
+                                              bool &done, unsigned *stg = nullptr, const RayRange &rg = RayRange()) {
     if (kAnyHit && done) return;
     if (kStages) ++stg[0];
     const V3 w0 = mk(o.x - T.t0[0], o.y - T.t0[1], o.z - T.t0[2]);
@@ -184,7 +195,9 @@ __device__ __forceinline__ void test_triangle(const TriRec &T, int t, V3 o, V3 d
     if (kStages) ++stg[4];
     const V3 e = sub(o, I);                                                     // distance, Vec3D.h:199-202
     const float dist = sqrtf(dot(e, e));
+    if (kRange != kRangeNone && !(dist >= rg.tmin)) return;
     if (dist < best || (kLex && dist == best && t < bidx)) {                  // :183
+        if (kRange == kRangeOpaque && rg.mats[rg.tri_mat[t]].transparent) return;
         best = dist; bidx = t; bI = I;
         if (kAnyHit) done = true;
     }
@@ -197,10 +210,10 @@ __device__ __forceinline__ TriRec leaf_rec(const DevScene &sc, int i) { return s
 
 // Scalar-load pipeline: records A and B alternate; each is fenced (s_waitcnt) before the next
 // record's s_load is issued, so one load is always in flight behind the arithmetic.
-template <bool kAnyHit>
+template <bool kAnyHit, int kRange = kRangeNone>
 __device__ __forceinline__ void closest_hit_loop(const TriRec *__restrict__ tris, int nt, V3 o, V3 dir, bool active,
-                                                 int &bidx, V3 &bI) {
-    float best = FLT_MAX;
+                                                 int &bidx, V3 &bI, const RayRange &rg = RayRange()) {
+    float best = kRange != kRangeNone ? rg.tmax : FLT_MAX;
     bool done = !active;
     if (nt <= 0) return;
     TriRec A = tris[0];
@@ -209,14 +222,14 @@ __device__ __forceinline__ void closest_hit_loop(const TriRec *__restrict__ tris
         if (kAnyHit && (t & 15) == 0 && __all(done)) return;
         sgpr_fence(A);
         const TriRec B = tris[t + 1];
-        test_triangle<kAnyHit>(A, t, o, dir, best, bidx, bI, done);
+        test_triangle<kAnyHit, false, false, false, kRange>(A, t, o, dir, best, bidx, bI, done, nullptr, rg);
         sgpr_fence(B);
         A = tris[min(t + 2, nt - 1)];
-        test_triangle<kAnyHit>(B, t + 1, o, dir, best, bidx, bI, done);
+        test_triangle<kAnyHit, false, false, false, kRange>(B, t + 1, o, dir, best, bidx, bI, done, nullptr, rg);
     }
     if (t < nt) {
         sgpr_fence(A);
-        test_triangle<kAnyHit>(A, t, o, dir, best, bidx, bI, done);
+        test_triangle<kAnyHit, false, false, false, kRange>(A, t, o, dir, best, bidx, bI, done, nullptr, rg);
     }
 }
 
@@ -341,9 +354,9 @@ __device__ __forceinline__ bool box_hit(const RayBox &R, float lx, float ly, flo
 // two records alternating so one load is in flight behind the arithmetic. Its tests reject r < 0 by
 // signs first (kSignFirst: uniform records, coherent rays); the walks' leaf loops do not (their lanes
 // hold different triangles, so every test would pay the check: measured 2% slower on C4).
-template <bool kAnyHit>
+template <bool kAnyHit, int kRange = kRangeNone>
 __device__ __forceinline__ void test_always(const DevScene &sc, V3 o, V3 dir, float &best, int &bidx, V3 &bI,
-                                            bool &done) {
+                                            bool &done, const RayRange &rg = RayRange()) {
     const int n = sc.n_always;
     if (n <= 0) return;
     const TriRec *__restrict__ recs = sc.always_recs;
@@ -353,14 +366,14 @@ __device__ __forceinline__ void test_always(const DevScene &sc, V3 o, V3 dir, fl
         if (kAnyHit && (i & 15) == 0 && __all(done)) return;
         sgpr_fence(A);
         const TriRec B = recs[i + 1];
-        test_triangle<kAnyHit, true, true>(A, static_cast<int>(sc.always[i]), o, dir, best, bidx, bI, done);
+        test_triangle<kAnyHit, true, true, false, kRange>(A, static_cast<int>(sc.always[i]), o, dir, best, bidx, bI, done, nullptr, rg);
         sgpr_fence(B);
         A = recs[min(i + 2, n - 1)];
-        test_triangle<kAnyHit, true, true>(B, static_cast<int>(sc.always[i + 1]), o, dir, best, bidx, bI, done);
+        test_triangle<kAnyHit, true, true, false, kRange>(B, static_cast<int>(sc.always[i + 1]), o, dir, best, bidx, bI, done, nullptr, rg);
     }
     if (i < n) {
         sgpr_fence(A);
-        test_triangle<kAnyHit, true, true>(A, static_cast<int>(sc.always[i]), o, dir, best, bidx, bI, done);
+        test_triangle<kAnyHit, true, true, false, kRange>(A, static_cast<int>(sc.always[i]), o, dir, best, bidx, bI, done, nullptr, rg);
     }
 }
 
@@ -368,21 +381,23 @@ __device__ __forceinline__ void test_always(const DevScene &sc, V3 o, V3 dir, fl
 // reaches the comparison with the current best.
 // (Skipping the divisions when their outcome is decided by signs or approximate quotients was
 // measured slower: the extra branches and registers cost more than the divisions they save.)
-template <bool kAnyHit>
+template <bool kAnyHit, int kRange = kRangeNone>
 __device__ __forceinline__ void test_leaf(const DevScene &sc, int first, int cnt, V3 o, V3 dir, float &best, int &bidx,
-                                          V3 &bI, bool &done) {
+                                          V3 &bI, bool &done, const RayRange &rg = RayRange()) {
     for (int k = 0; k < cnt; ++k) {
         const TriRec T = leaf_rec(sc, first + k);
-        test_triangle<kAnyHit, true>(T, static_cast<int>(sc.leaf_idx[first + k]), o, dir, best, bidx, bI, done);
+        test_triangle<kAnyHit, true, false, false, kRange>(T, static_cast<int>(sc.leaf_idx[first + k]), o, dir, best, bidx, bI, done,
+                                                           nullptr, rg);
     }
 }
 
-template <bool kAnyHit>
+template <bool kAnyHit, int kRange = kRangeNone>
 __device__ __forceinline__ void bvh_query(const DevScene &sc, V3 o, V3 dir, bool active, int &bidx, V3 &bI,
-                                          const LaneStack &stack, unsigned &tests, unsigned &visits) {
-    float best = FLT_MAX;
+                                          const LaneStack &stack, unsigned &tests, unsigned &visits,
+                                          const RayRange &rg = RayRange()) {
+    float best = kRange != kRangeNone ? rg.tmax : FLT_MAX;   // a bound, not a found hit: see bvh4_query_ww
     bool done = !active;
-    test_always<kAnyHit>(sc, o, dir, best, bidx, bI, done);
+    test_always<kAnyHit, kRange>(sc, o, dir, best, bidx, bI, done, rg);
     if (!active || (kAnyHit && done)) return;
     RayBox R;
     R.o = o;
@@ -408,7 +423,8 @@ __device__ __forceinline__ void bvh_query(const DevScene &sc, V3 o, V3 dir, bool
             float t0, t1;
             bool h0 = box_hit(R, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, t0);
             bool h1 = box_hit(R, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, t1);
-            if (!kAnyHit) {   // distance cull: no accepted point of the child is nearer than its entry
+            if (!kAnyHit || kRange != kRangeNone) {   // distance cull: no accepted point of the child is nearer than its entry
+                // (ranged any-hit: best stays tmax, and nothing at or beyond tmax counts)
                 h0 = h0 && (t0 * R.dlen - R.pad) * 0.99999f <= best;
                 h1 = h1 && (t1 * R.dlen - R.pad) * 0.99999f <= best;
             }
@@ -429,7 +445,7 @@ __device__ __forceinline__ void bvh_query(const DevScene &sc, V3 o, V3 dir, bool
             const uint32_t u = static_cast<uint32_t>(ref);
             const int cnt = static_cast<int>((u >> kBvhCountShift) & kBvhCountMask);
             const int first = static_cast<int>(u & ((1u << kBvhCountShift) - 1u));
-            test_leaf<kAnyHit>(sc, first, cnt, o, dir, best, bidx, bI, done);
+            test_leaf<kAnyHit, kRange>(sc, first, cnt, o, dir, best, bidx, bI, done, rg);
             tests += static_cast<unsigned>(cnt);
             if (kAnyHit && done) break;
             if (sp == 0) break;
@@ -485,16 +501,16 @@ __device__ __forceinline__ float cull_param(const Ray4 &R, float best, float pad
     return (best * 1.00002f + pad) * R.inv_dlen;
 }
 
-template <bool kAnyHit>
+template <bool kAnyHit, int kRange = kRangeNone>
 __device__ __forceinline__ float node_lim(float tx, float tcull) {
     const float txs = tx * 1.00001f;   // the 1e-5 relative slack of te <= tx
-    if (kAnyHit) return txs;
+    if (kAnyHit && kRange == kRangeNone) return txs;   // (a ranged any-hit walk culls by its tmax)
     return fminf(txs, tcull);
 }
 
 // One node visit: the wanted children by entry distance, the far ones pushed; returns the next ref
 // (the nearest wanted child, else the stack top, else kDoneRef). Entries [base, sp) are this walk's.
-template <bool kAnyHit>
+template <bool kAnyHit, int kRange = kRangeNone>
 __device__ __forceinline__ int32_t node4_next(const Ray4 &R, const Node4Rows &nd, const LaneStack &stack, int &sp,
                                               int base = 0) {
     // te <= tx (1 + 1e-5) and, closest-hit, te <= tcull, as one compare against their minimum.
@@ -517,7 +533,7 @@ __device__ __forceinline__ int32_t node4_next(const Ray4 &R, const Node4Rows &nd
             const float tnz = fmaf(nz[k], R.az.x, R.az.y), tfz = fmaf(fz[k], R.az.x, R.fzc.x);
             const float te = fmaxf(fmaxf(fmaxf(tnx, tny), tnz), 0.0f);
             const float tx = fminf(fminf(tfx, tfy), tfz);
-            tc[k] = te <= node_lim<kAnyHit>(tx, tcull) ? te : INFINITY;
+            tc[k] = te <= node_lim<kAnyHit, kRange>(tx, tcull) ? te : INFINITY;
         }
     }
     if (!kAnyHit) {
@@ -613,23 +629,36 @@ __device__ __forceinline__ void ray4_setup(const DevScene &sc, V3 o, V3 dir, Ray
     R.rows[3] = (nx ? kLo : kHi); R.rows[4] = (ny ? kLo : kHi) + kRow; R.rows[5] = (nz ? kLo : kHi) + 2 * kRow;
 }
 
-template <bool kAnyHit>
+// Ranged walks (kRange): best starts at tmax, a bound that no triangle found yet stands behind. The cull
+// argument of bvh.cpp never uses that best is a hit, only that nothing at a distance above best can be
+// the answer: a child is skipped when its entry parameter exceeds tcull, which (cull_param) puts every
+// accepted point inside it at a distance above best (1 + 1e-5), and a triangle at a distance >= tmax is
+// out of range (the update's strict '<' against best = tmax). So the walk culls by tmax from its first
+// node, lowers best at every in-range hit as before, and the result is the lexicographic (distance, index)
+// minimum over the in-range accepted triangles. A ranged any-hit walk never lowers best (it ends at its
+// first counted triangle), so its tcull stays cull_param(tmax) and node_lim applies it. The lower bound
+// takes no part in the cull (a subtree that ends before tmin is still walked; its triangles fail the
+// dist >= tmin test). Rays whose cull is off (inv_dlen +inf: tcull = +inf for any tmax > 0) walk by the
+// slab test alone, as before.
+template <bool kAnyHit, int kRange = kRangeNone>
 __device__ __forceinline__ void bvh4_query_ww(const DevScene &sc, V3 o, V3 dir, bool active, int &bidx, V3 &bI,
-                                              const LaneStack &stack, unsigned &tests, unsigned &visits) {
-    float best = FLT_MAX;
+                                              const LaneStack &stack, unsigned &tests, unsigned &visits,
+                                              const RayRange &rg = RayRange()) {
+    float best = kRange != kRangeNone ? rg.tmax : FLT_MAX;
     bool done = !active;
-    test_always<kAnyHit>(sc, o, dir, best, bidx, bI, done);
+    test_always<kAnyHit, kRange>(sc, o, dir, best, bidx, bI, done, rg);
     if (!active || (kAnyHit && done)) return;
     Ray4 R;
     float pad;
     ray4_setup(sc, o, dir, R, pad);
+    if (kRange != kRangeNone) R.fzc.y = cull_param(R, best, pad);   // (best: tmax, or an always-list hit below it)
     int sp = 0;
     int32_t node = 0;          // inner node to visit, a leaf ref, or kDoneRef
     int32_t leaf = kDoneRef;   // the postponed leaf
     while (true) {
         while (node >= 0) {
             ++visits;
-            node = node4_next<kAnyHit>(R, load_node4(sc.nodes4f, node, R.rows), stack, sp);
+            node = node4_next<kAnyHit, kRange>(R, load_node4(sc.nodes4f, node, R.rows), stack, sp);
             if (node < 0 && node != kDoneRef && leaf == kDoneRef) {   // postpone it, keep walking
                 leaf = node;
                 node = stack.pop_or(sp, 0, kDoneRef);
@@ -643,7 +672,8 @@ __device__ __forceinline__ void bvh4_query_ww(const DevScene &sc, V3 o, V3 dir, 
             // one triangle per iteration: the ref is the cursor (first + 1, count - 1), so a lane
             // whose leaf ends goes on to its next leaf while the others test their next triangle
             const TriRec T = leaf_rec(sc, first);
-            test_triangle<kAnyHit, true>(T, static_cast<int>(sc.leaf_idx[first]), o, dir, best, bidx, bI, done);
+            test_triangle<kAnyHit, true, false, false, kRange>(T, static_cast<int>(sc.leaf_idx[first]), o, dir, best, bidx, bI, done,
+                                                               nullptr, rg);
             ++tests;
             if (kAnyHit && done) { node = kDoneRef; break; }
             if (cnt > 1) {
@@ -987,12 +1017,14 @@ __device__ __forceinline__ void bvh4_query_quad(const DevScene &sc, V3 o, V3 dir
 
 // The closest-hit / any-hit query of the tree kernels: W = 4 the four-wide while-while walk (or,
 // kSteal, its in-wave stealing form), W = 2 the binary tree (scenes above 1e6 in magnitude).
-template <bool kAnyHit, int W, bool kSteal = false>
+template <bool kAnyHit, int W, bool kSteal = false, int kRange = kRangeNone>
 __device__ __forceinline__ void bvh_query_w(const DevScene &sc, V3 o, V3 dir, bool active, int &bidx, V3 &bI,
-                                            const LaneStack &stack, unsigned &tests, unsigned &visits) {
+                                            const LaneStack &stack, unsigned &tests, unsigned &visits,
+                                            const RayRange &rg = RayRange()) {
+    static_assert(!kSteal || kRange == kRangeNone, "the stealing walk has no ranged form");
     if (W == 4 && kSteal) bvh4_query_steal<kAnyHit>(sc, o, dir, active, bidx, bI, stack, tests, visits);
-    else if (W == 4) bvh4_query_ww<kAnyHit>(sc, o, dir, active, bidx, bI, stack, tests, visits);
-    else bvh_query<kAnyHit>(sc, o, dir, active, bidx, bI, stack, tests, visits);
+    else if (W == 4) bvh4_query_ww<kAnyHit, kRange>(sc, o, dir, active, bidx, bI, stack, tests, visits, rg);
+    else bvh_query<kAnyHit, kRange>(sc, o, dir, active, bidx, bI, stack, tests, visits, rg);
 }
 
 // XCD-aware work split (cdna_hip_programming.md T1): blocks are dealt round-robin over the 8 XCDs,
@@ -1450,6 +1482,142 @@ __global__ __launch_bounds__(kBlock) void k_query_rays(const TriRec *__restrict_
     V3 bI = mk(0, 0, 0);
     closest_hit_loop<kMode == kQueryOccludedAny>(tris, nt, o, dir, active, bidx, bI);
     if (active) store_query<kMode>(tri_mat, mats, j, bidx, bI, idx, point, blocked);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Ranged device queries (rt_closest_hit_range_device, rt_occluded_range_device): the queries above with a
+// per-ray distance range [tmin, tmax) and, for the closest hit, a 16-byte record {triangle, distance, s, t}
+// instead of the index. The walks are the kRange forms (test_triangle, bvh4_query_ww).
+// kRangeClosest: the lexicographic (distance, index) minimum over the in-range accepted triangles.
+// kRangeOccludedClosest: isShadow's rule inside the range (that triangle's material), when some material
+// in use is transparent.
+// kRangeOccludedAny: either occlusion rule when no material in use is transparent, by the any-hit walk.
+// kRangeOccludedAnyOpaque: "some in-range accepted triangle is not transparent": the any-hit walk that
+// passes over transparent triangles (kRangeOpaque).
+// Whether the bound arrays are given is a wave-uniform runtime test (scalar branches), not a template
+// parameter. A ray whose range is empty (a NaN bound, tmax <= 0, tmin >= tmax) takes no part in the walk
+// and reports a miss.
+// ---------------------------------------------------------------------------------------------
+enum : int { kRangeClosest = 0, kRangeOccludedClosest = 1, kRangeOccludedAny = 2, kRangeOccludedAnyOpaque = 3 };
+constexpr bool range_any_hit(int mode) { return mode == kRangeOccludedAny || mode == kRangeOccludedAnyOpaque; }
+constexpr int range_kind(int mode) { return mode == kRangeOccludedAnyOpaque ? kRangeOpaque : kRangeBounded; }
+
+// Ray j's bounds, clamped above to FLT_MAX (where the half-line walk's best starts; a NaN stays a NaN), and
+// whether the range holds anything. to_dest (RT_RANGE_TO_DEST, only without d_tmax): tmax = |dest - origin|
+// as the reference's Vec3D length, sqrtf((dx dx + dy dy) + dz dz).
+__device__ __forceinline__ bool load_range(const float *__restrict__ d_tmin, const float *__restrict__ d_tmax, bool to_dest,
+                                           int j, V3 dir, RayRange &rg) {
+    const float lo = d_tmin ? d_tmin[j] : 0.0f;
+    const float hi = d_tmax ? d_tmax[j] : to_dest ? sqrtf(dot(dir, dir)) : FLT_MAX;
+    rg.tmin = lo > FLT_MAX ? FLT_MAX : lo;
+    rg.tmax = hi > FLT_MAX ? FLT_MAX : hi;
+    return rg.tmin < rg.tmax && rg.tmax > 0.0f;
+}
+
+// The hit record of triangle bidx for this ray: test_triangle's arithmetic again on the same record (the
+// scene's records in index order hold the bytes of the leaf-ordered and always-list copies) and the same
+// ray, so the same bits as the test that won, as the stealing walk's owner relies on. Recomputed after
+// the walk and not carried through it: dist, s and t would be three more registers live across every
+// node visit of kernels built to the walk's register budget, for one division pair per ray saved.
+__device__ __forceinline__ int4 hit_record(const TriRec &T, int bidx, V3 o, V3 dir) {
+    const V3 w0 = mk(o.x - T.t0[0], o.y - T.t0[1], o.z - T.t0[2]);
+    const float b = T.n[0] * dir.x + T.n[1] * dir.y + T.n[2] * dir.z;          // :113
+    const float a = -(T.n[0] * w0.x + T.n[1] * w0.y + T.n[2] * w0.z);          // :114
+    const float r = a / b;                                                      // :124
+    const V3 I = mk(o.x + dir.x * r, o.y + dir.y * r, o.z + dir.z * r);         // :130
+    const V3 w = mk(I.x - T.t0[0], I.y - T.t0[1], I.z - T.t0[2]);               // :137
+    const float wu = w.x * T.u[0] + w.y * T.u[1] + w.z * T.u[2];                 // :138
+    const float wv = w.x * T.v[0] + w.y * T.v[1] + w.z * T.v[2];                 // :139
+    const float s = (T.uv * wv - T.vv * wu) / T.D;                              // :144
+    const float tt = (T.uv * wu - T.uu * wv) / T.D;                             // :148
+    const V3 e = sub(o, I);
+    const float dist = sqrtf(dot(e, e));
+    return make_int4(bidx, as_int(dist), as_int(s), as_int(tt));
+}
+
+template <int kMode>
+__device__ __forceinline__ void store_range(const TriRec *__restrict__ tris, const uint32_t *__restrict__ tri_mat,
+                                            const DevMaterial *__restrict__ mats, int j, int bidx, V3 bI, V3 o, V3 dir,
+                                            int4 *__restrict__ hit, float *__restrict__ point, uint8_t *__restrict__ blocked) {
+    if (kMode == kRangeClosest) {
+        int4 rec = make_int4(-1, as_int(INFINITY), 0, 0);
+        if (bidx >= 0) rec = hit_record(tris[bidx], bidx, o, dir);
+        hit[j] = rec;                                                              // one 16-byte store
+        if (point) reinterpret_cast<V3 *>(point)[j] = bI;
+    } else if (kMode == kRangeOccludedClosest) {
+        uint8_t sh = 0;
+        if (bidx >= 0) sh = mats[tri_mat[bidx]].transparent ? 0 : 1;               // :253-257
+        blocked[j] = sh;
+    } else {
+        blocked[j] = bidx >= 0 ? 1 : 0;   // the walk counted only blocking triangles
+    }
+}
+
+struct RangeQuery {
+    const float *tmin, *tmax;   // per ray, or null
+    int32_t to_dest;
+    int4 *hit;                  // kRangeClosest: the records; point may be null
+    float *point;
+    uint8_t *blocked;           // the occlusion modes
+};
+
+template <int W, int kMode, int kStride, bool kCount>
+__global__ __launch_bounds__(kBvhBlock) void k_bvh_range_rays(const DevScene sc, const void *__restrict__ org,
+                                                              const void *__restrict__ dst, int n,
+                                                              const int32_t *__restrict__ d_count, const RangeQuery q) {
+    extern __shared__ int32_t lds_stack[];
+    const LaneStack stack = lane_stack(sc, lds_stack);
+    WorkTally<kCount> wt;
+    drive_queries(live_rays(d_count, n), 0, nullptr, [&](int j, int end) {
+        const bool active = j < end;
+        V3 o = mk(0, 0, 0), dir = mk(0, 0, 0);
+        RayRange rg;
+        rg.tri_mat = sc.tri_mat;
+        rg.mats = sc.mats;
+        bool walk = false;
+        if (active) {
+            o = load_ray_point<kStride>(org, j);
+            dir = sub(load_ray_point<kStride>(dst, j), o);                          // :111
+            walk = load_range(q.tmin, q.tmax, q.to_dest != 0, j, dir, rg);
+        }
+        int bidx = -1;
+        V3 bI = mk(0, 0, 0);
+        wt.begin();
+        bvh_query_w<range_any_hit(kMode), W, false, range_kind(kMode)>(sc, o, dir, walk, bidx, bI, stack, wt.tests, wt.visits, rg);
+        wt.end();
+        // (a closest-hit walk tests the always list for its idle lanes too: an empty range is a miss)
+        if (!walk) { bidx = -1; bI = mk(0, 0, 0); }
+        if (active) store_range<kMode>(sc.tris, sc.tri_mat, sc.mats, j, bidx, bI, o, dir, q.hit, q.point, q.blocked);
+    });
+    wt.flush(kMode == kRangeClosest ? sc.work : sc.work ? sc.work + kWorkFields : nullptr);
+}
+
+// The same over every triangle in index order (RT_ACCEL_BRUTE_FORCE, or no tree could be built).
+template <int kMode, int kStride>
+__global__ __launch_bounds__(kBlock) void k_range_rays(const TriRec *__restrict__ tris, int nt, const uint32_t *__restrict__ tri_mat,
+                                                       const DevMaterial *__restrict__ mats, const void *__restrict__ org,
+                                                       const void *__restrict__ dst, int n, const int32_t *__restrict__ d_count,
+                                                       const RangeQuery q) {
+    const int live = live_rays(d_count, n);
+    const int64_t base = static_cast<int64_t>(blockIdx.x) * kBlock;
+    if (base >= live) return;
+    const bool active = base + threadIdx.x < live;
+    const int j = active ? static_cast<int>(base + threadIdx.x) : 0;
+    V3 o = mk(0, 0, 0), dir = mk(0, 0, 0);
+    RayRange rg;
+    rg.tri_mat = tri_mat;
+    rg.mats = mats;
+    bool walk = false;
+    if (active) {
+        o = load_ray_point<kStride>(org, j);
+        dir = sub(load_ray_point<kStride>(dst, j), o);
+        walk = load_range(q.tmin, q.tmax, q.to_dest != 0, j, dir, rg);
+    }
+    int bidx = -1;
+    V3 bI = mk(0, 0, 0);
+    closest_hit_loop<range_any_hit(kMode), range_kind(kMode)>(tris, nt, o, dir, walk, bidx, bI, rg);
+    if (!walk) { bidx = -1; bI = mk(0, 0, 0); }
+    if (active) store_range<kMode>(tris, tri_mat, mats, j, bidx, bI, o, dir, q.hit, q.point, q.blocked);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -4156,6 +4324,41 @@ void launch_query_rays(const DevScene &s, bool occluded, const void *org, const 
         if (wide) launch_query_mode<kQueryOccludedAny, 4>(s, org, dst, n, d_count, idx, point, blocked, stream);
         else launch_query_mode<kQueryOccludedAny, 3>(s, org, dst, n, d_count, idx, point, blocked, stream);
     }
+}
+
+namespace {
+template <int kMode, int kStride>
+void launch_range_mode(const DevScene &s0, const void *org, const void *dst, int32_t n, const int32_t *d_count, const RangeQuery &q,
+                       hipStream_t stream) {
+    if (s0.use_bvh) {   // launch_query_mode's shape
+        const int W = s0.bvh_width == 4 ? 4 : 2;
+        const DevScene s = for_width(s0, W);
+        auto k = W == 4 ? (s.work ? k_bvh_range_rays<4, kMode, kStride, true> : k_bvh_range_rays<4, kMode, kStride, false>)
+                        : (s.work ? k_bvh_range_rays<2, kMode, kStride, true> : k_bvh_range_rays<2, kMode, kStride, false>);
+        hipLaunchKernelGGL(k, dim3(grid_bvh(n, s.bvh_grid)), dim3(kBvhBlock), bvh_lds(s), stream, s, org, dst, n, d_count, q);
+        return;
+    }
+    hipLaunchKernelGGL((k_range_rays<kMode, kStride>), dim3(grid_for(n)), dim3(kBlock), 0, stream, s0.tris, s0.nt, s0.tri_mat,
+                       s0.mats, org, dst, n, d_count, q);
+}
+
+template <int kMode>
+void launch_range_stride(const DevScene &s, const void *org, const void *dst, int32_t ray_stride, int32_t n, const int32_t *d_count,
+                         const RangeQuery &q, hipStream_t stream) {
+    if (ray_stride == 4) launch_range_mode<kMode, 4>(s, org, dst, n, d_count, q, stream);
+    else launch_range_mode<kMode, 3>(s, org, dst, n, d_count, q, stream);
+}
+}  // namespace
+
+void launch_range_rays(const DevScene &s, bool occluded, bool any_opaque, bool to_dest, const void *org, const void *dst,
+                       int32_t ray_stride, int32_t n, const int32_t *d_count, const float *d_tmin, const float *d_tmax, void *hit,
+                       float *point, uint8_t *blocked, hipStream_t stream) {
+    if (n <= 0) return;
+    const RangeQuery q{d_tmin, d_tmax, to_dest ? 1 : 0, static_cast<int4 *>(hit), point, blocked};
+    if (!occluded) launch_range_stride<kRangeClosest>(s, org, dst, ray_stride, n, d_count, q, stream);
+    else if (!s.any_transparent) launch_range_stride<kRangeOccludedAny>(s, org, dst, ray_stride, n, d_count, q, stream);   // either rule
+    else if (any_opaque) launch_range_stride<kRangeOccludedAnyOpaque>(s, org, dst, ray_stride, n, d_count, q, stream);
+    else launch_range_stride<kRangeOccludedClosest>(s, org, dst, ray_stride, n, d_count, q, stream);
 }
 
 void launch_gen_rays_device(const void *org, const void *dst, int32_t ray_stride, int32_t n, const DevWork &w, hipStream_t stream) {
