@@ -165,6 +165,17 @@ int rt_work_detail(rt_scene *scene, int32_t kind, uint64_t out[RT_WORK_FIELDS]);
  * and stamp builds were retired with the variants they measured); 0 in production builds.
  * Reads count words from offset (offset + count <= 131072); synchronises the device. */
 int rt_diag_read(rt_scene *scene, int64_t offset, int64_t count, uint64_t *out);
+/* The two numerics functions of the device's shade() on their own, for tests that compare them with their
+ * host statements over inputs no frame produces: out[i] = the kernels' powf(x[i], y[i]) of the specular term
+ * (RT_DIAG_SPEC_POW; raytracert_amd/csrc/spec_pow.h) or their glibc powf(x[i], 2) of refraction()
+ * (RT_DIAG_POWF2, with the scene's own device tie table; y may be NULL; |x| >= 2, outside a dot product of
+ * unit vectors and outside the table, gives x * x). x, y, out: host arrays of n floats; synchronous, as
+ * rt_ray_intersect_triangle. RT_E_ARG, with out untouched: a NULL or host-only scene, another kind, n < 0 or
+ * above RT_DIAG_MATH_MAX, with n > 0 a NULL array. n == 0 succeeds and touches nothing. */
+#define RT_DIAG_SPEC_POW 0
+#define RT_DIAG_POWF2    1
+#define RT_DIAG_MATH_MAX (1 << 28)
+int rt_diag_math(rt_scene *scene, int32_t kind, const float *x, const float *y, int64_t n, float *out);
 /* The per-view launch trials of render pipeline 0 (RT_TUNE_WAVE_STEAL 2 x RT_TUNE_CHAIN_SPLIT 5 x
  * RT_TUNE_SHADOW_HELPERS 2 x RT_TUNE_STEAL_QUARTER -1): info = {candidates timed (0 while pending),
  * chosen candidate (-1 pending), its wave_steal, its chain distribution, its shadow helpers, its

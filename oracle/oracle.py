@@ -5,6 +5,7 @@ cpu_baseline leg. The product package (raytracert_amd) never imports this module
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -63,8 +64,54 @@ def lib():
         L.ora_default_corners.argtypes = [C.c_int32, C.c_int32, C.c_void_p]
         L.ora_debug_trace.argtypes = [C.c_void_p, C.POINTER(OraParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.ora_debug_trace.restype = C.c_int32
+        L.ora_set_spec_pow.argtypes = [C.c_int]
+        L.ora_set_spec_pow.restype = C.c_int
+        L.ora_spec_pow_twin.argtypes = [C.c_float, C.c_float]
+        L.ora_spec_pow_twin.restype = C.c_float
+        L.ora_spec_pow_twin_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.ora_powf_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         _lib = L
     return _lib
+
+
+def _pow_batch(fn, x, y):
+    x = np.ascontiguousarray(x, np.float32).reshape(-1)
+    y = np.ascontiguousarray(y, np.float32).reshape(-1)
+    if len(x) != len(y):
+        raise ValueError("x and y differ in length")
+    out = np.zeros(len(x), np.float32)
+    fn(_ptr(x), _ptr(y), len(x), _ptr(out))
+    return out
+
+
+def spec_pow_twin(x, y) -> np.ndarray:
+    """The host build of the kernels' spec_pow.h, element by element (ora_spec_pow_twin_batch)."""
+    return _pow_batch(lib().ora_spec_pow_twin_batch, x, y)
+
+
+def libm_powf(x, y) -> np.ndarray:
+    """This platform's powf, element by element (ora_powf_batch)."""
+    return _pow_batch(lib().ora_powf_batch, x, y)
+
+
+_SPEC_POW = {"glibc": 0, "twin": 1}
+
+
+def set_spec_pow(which: str) -> None:
+    """ora_set_spec_pow: the powf of blinnPhongSpecularOnly is glibc's ("glibc", the default) or the host
+    build of the kernels' spec_pow.h ("twin"). Process-wide: set it before a render or trace, never during one."""
+    if which not in _SPEC_POW or lib().ora_set_spec_pow(_SPEC_POW[which]) != 0:
+        raise ValueError(f"set_spec_pow: {which!r} is neither 'glibc' nor 'twin'")
+
+
+@contextlib.contextmanager
+def spec_pow(which: str):
+    """`with spec_pow("twin"):` renders and traces with that function, and restores glibc's on the way out."""
+    set_spec_pow(which)
+    try:
+        yield
+    finally:
+        set_spec_pow("glibc")
 
 
 def _ptr(a: np.ndarray):

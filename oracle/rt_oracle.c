@@ -404,6 +404,24 @@ static vec3 diffuse_only(const material *m, vec3 *normal, vec3 lightpos) {
     return Diffuse;
 }
 
+/* Which function evaluates powf(spec, Ns) of blinnPhongSpecularOnly (ora_set_spec_pow): 0 glibc powf, the
+ * reference's call and the default; 1 the host build of the kernels' own spec_pow.h (spec_pow_twin.cpp),
+ * against which the kernels' colours are compared bit for bit. Set before a render or trace, never during one. */
+float ora_spec_pow_twin(float x, float y);
+static int g_spec_pow = 0;
+
+int ora_set_spec_pow(int which) {
+    if (which != 0 && which != 1) return -1;
+    g_spec_pow = which;
+    return 0;
+}
+
+/* This platform's powf over arrays, for tests of the kernels' restatements of it (a million ctypes calls of
+ * libm take seconds). The exponent comes from memory, so the compiler cannot fold powf(x, 2) into x * x. */
+void ora_powf_batch(const float *x, const float *y, int64_t n, float *out) {
+    for (int64_t i = 0; i < n; i++) out[i] = powf(x[i], y[i]);
+}
+
 /* blinnPhongSpecularOnly, raytracing.cpp:210-232 */
 static vec3 blinn_phong_specular_only(const ctx *c, vec3 vertexPos, vec3 *normal, const material *m, vec3 lightpos) {
     vec3 Specularity = V(0, 0, 0);
@@ -416,7 +434,7 @@ static vec3 blinn_phong_specular_only(const ctx *c, vec3 vertexPos, vec3 *normal
     vec3 H = vadd(Vv, L);
     vnormalize(&H);
     float spec = fmax_std(vdot(H, *normal), 0.0f);
-    spec = powf(spec, m->Ns);
+    spec = g_spec_pow ? ora_spec_pow_twin(spec, m->Ns) : powf(spec, m->Ns);
     Specularity = vadd(Specularity, vscale(m->Ks, spec));
     return Specularity;
 }

@@ -95,6 +95,17 @@ void ora_perform_ray_tracing(const ora_scene *s, const ora_params *p, const floa
 void ora_render(const ora_scene *s, const ora_params *p, int32_t x0, int32_t y0, int32_t w, int32_t h,
                 float *rgb_f32, uint8_t *rgb_u8, int32_t nthreads, uint64_t counts[3]);
 
+/* The powf of blinnPhongSpecularOnly (raytracing.cpp:226), and only that one: which = 0 glibc powf (the
+ * reference's call; the default), 1 the host build of raytracert_amd/csrc/spec_pow.h (spec_pow_twin.cpp), the
+ * function the kernels evaluate. Process-wide; set it before a render or trace, never during one. Returns 0, or
+ * -1 for another value (nothing changes). */
+int ora_set_spec_pow(int which);
+/* That host build itself: rt::spec_pow(x, y) compiled by g++ -O2 -ffp-contract=off. */
+float ora_spec_pow_twin(float x, float y);
+/* Both over arrays of n floats: the twin, and this platform's libm powf (the exponent read from memory). */
+void ora_spec_pow_twin_batch(const float *x, const float *y, int64_t n, float *out);
+void ora_powf_batch(const float *x, const float *y, int64_t n, float *out);
+
 /* Default camera of main.cpp:217-222,288-325: modelview = translate(0,0,-4), projection =
  * gluPerspective(50, w/h, 1, 10), viewport (0,0,w,h); corner rays by gluUnProject at win-z 0/1,
  * with double-precision matrices. Writes the 8 corner vectors (order as ora_params.corners). */

@@ -61,6 +61,7 @@ DEFAULT_SEED = 0x5EED
 LOAD_PARALLEL, LOAD_SEQUENTIAL = 0, 1
 LOAD_TEXCOORDS = 0x10
 WORK_FIELDS = 6
+DIAG_SPEC_POW, DIAG_POWF2 = 0, 1        # rt_diag_math kinds
 RAYS_PACKED, RAYS_PADDED = 3, 4         # ray_stride of the device-resident query entries
 RANGE_TO_DEST, OCCLUDE_ANY_OPAQUE = 1 << 0, 1 << 1   # flags of the ranged device queries
 HIT_BYTES = 16                          # sizeof(rt_hit): int32 triangle, float distance, s, t
@@ -161,6 +162,7 @@ _SIGNATURES = {
     "rt_scene_bvh_info": ([_VP, _VP], C.c_int),
     "rt_work_detail": ([_VP, C.c_int32, _VP], C.c_int),
     "rt_diag_read": ([_VP, C.c_int64, C.c_int64, _VP], C.c_int),
+    "rt_diag_math": ([_VP, C.c_int32, _VP, _VP, C.c_int64, _VP], C.c_int),
     "rt_workspace_bytes": ([_VP, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int),
     "rt_workspace_layout": ([C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_uint64), _VP], C.c_int),
     "rt_batch_durations": ([_VP, _VP, C.c_int64, C.POINTER(C.c_int64)], C.c_int),

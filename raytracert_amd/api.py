@@ -713,6 +713,18 @@ class Scene:
         check(lib().rt_diag_read(self._h, offset, count, _ptr(d)))
         return d
 
+    def diag_math(self, kind, x, y=None) -> np.ndarray:
+        """rt_diag_math: the device's specular powf(x, y) ('spec_pow') or its glibc powf(x, 2) with this
+        scene's tie table ('powf2'; y unused), element by element over float32 host arrays."""
+        k = {"spec_pow": _capi.DIAG_SPEC_POW, "powf2": _capi.DIAG_POWF2}.get(kind, kind)
+        xs = np.ascontiguousarray(x, np.float32).reshape(-1)
+        ys = None if y is None else np.ascontiguousarray(y, np.float32).reshape(-1)
+        if ys is not None and len(ys) != len(xs):
+            raise ValueError("diag_math: x and y differ in length")
+        out = np.zeros(len(xs), np.float32)
+        check(lib().rt_diag_math(self._h, int(k), _ptr(xs), _ptr(ys), len(xs), _ptr(out)))
+        return out
+
     def work_detail(self, kind: int = _capi.KERNEL_CLOSEST_HIT) -> dict:
         """Full BVH work counters of `kind` (rt_work_detail): tests, visits, the per-wave-task
         maxima that give the traversal's SIMD efficiency, the longest query."""

@@ -334,5 +334,8 @@ void launch_assemble_tiles(const uint8_t *gathered, int32_t width, int32_t heigh
                            int32_t nranks, uint8_t *out, hipStream_t stream, int64_t slot0 = 0, int64_t nslots = -1);
 // rayIntersectTriangle for n (ray, triangle) pairs: R = n x (origin, dest), T = n x 3 vertices
 void launch_ray_triangle_pairs(const float *R, const float *T, int32_t n, uint8_t *hit, float *I, hipStream_t stream);
+// rt_diag_math: out[i] = spec_powf(x[i], y[i]) (kind 0) or glibc_powf2(x[i]) with s.ties (kind 1; y unread),
+// the device functions shade_hit calls, for n < 2^31 device elements
+void launch_diag_math(const DevScene &s, int32_t kind, const float *x, const float *y, int64_t n, float *out, hipStream_t stream);
 
 }  // namespace rt

@@ -3833,6 +3833,17 @@ __global__ __launch_bounds__(kBlock) void k_ray_triangle_pairs(const float *__re
     I[3 * i] = out.x; I[3 * i + 1] = out.y; I[3 * i + 2] = out.z;
 }
 
+// rt_diag_math: the two device numerics functions of shade_hit on their own, one element per thread, so a
+// test compares them with their host statements over inputs no frame produces. kind 0: spec_powf(x, y);
+// kind 1: glibc_powf2(x) with the scene's tie table (y not read).
+__global__ __launch_bounds__(kBlock) void k_diag_math(int32_t kind, const float *__restrict__ x, const float *__restrict__ y,
+                                                      int64_t n, const uint32_t *__restrict__ ties, int32_t n_ties,
+                                                      float *__restrict__ out) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (i >= n) return;
+    out[i] = kind == 0 ? spec_powf(x[i], y[i]) : glibc_powf2(x[i], ties, n_ties);
+}
+
 // Un-permute of gathered tile shards (multi-GPU frame): gathered = [rank][nslots]
 // tiles of tw x th x 3 bytes, the slots slot0 .. slot0 + nslots - 1 of every rank's shard (one gather
 // chunk; the whole shard when slot0 = 0, nslots = slots); global tile id g = f * T + t is held by rank
@@ -4506,6 +4517,11 @@ void launch_refit_level2(BvhNode *nodes, const int32_t *ids, int32_t n, const fl
 void launch_ray_triangle_pairs(const float *R, const float *T, int32_t n, uint8_t *hit, float *I, hipStream_t stream) {
     if (n <= 0) return;
     hipLaunchKernelGGL(k_ray_triangle_pairs, dim3(grid_for(n)), dim3(kBlock), 0, stream, R, T, n, hit, I);
+}
+
+void launch_diag_math(const DevScene &s, int32_t kind, const float *x, const float *y, int64_t n, float *out, hipStream_t stream) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_diag_math, dim3(grid_for(n)), dim3(kBlock), 0, stream, kind, x, y, n, s.ties, s.n_ties, out);
 }
 
 void launch_assemble_tiles(const uint8_t *gathered, int32_t width, int32_t height, int32_t tw, int32_t th, int32_t frames,

@@ -3,7 +3,8 @@
 // double-double log on accuracy a float result never sees; this form is ~4e-14 relative, so its
 // float rounding equals the correctly rounded powf except within ~1e-6 of a rounding midpoint
 // (one float ulp there; colour-only, as glibc powf itself is not correctly rounded everywhere).
-// Header-only and host-callable so tests/cxx/spec_pow_check.cpp checks the same code on the CPU.
+// Header-only and host-callable so tests/cxx/spec_pow_check.cpp checks the same code on the CPU;
+// tests/test_gpu_device_math.py checks that the device build gives the host build's bits.
 #ifndef RT_SPEC_POW_H_
 #define RT_SPEC_POW_H_
 

@@ -9,7 +9,8 @@ CXXFLAGS := -std=c++17 -ffp-contract=off -fno-fast-math -pthread $(SAN) -I$(ROOT
             -I$(ROOT)/raytracert_amd/csrc -I$(ROOT)/oracle
 CFLAGS  := -std=gnu11 -ffp-contract=off -fno-fast-math -pthread $(SAN)
 SRCS    := $(ROOT)/raytracert_amd/csrc/scene_loader.cpp $(ROOT)/raytracert_amd/csrc/obj_parallel.cpp \
-           $(ROOT)/raytracert_amd/csrc/bvh.cpp $(ROOT)/tests/cxx/loader_san.cpp
+           $(ROOT)/raytracert_amd/csrc/bvh.cpp $(ROOT)/tests/cxx/loader_san.cpp \
+           $(ROOT)/oracle/spec_pow_twin.cpp
 
 $(OUT)/loader_san: $(SRCS) $(OUT)/rt_oracle.o
 	g++ $(CXXFLAGS) -o $@ $(SRCS) $(OUT)/rt_oracle.o -lm
