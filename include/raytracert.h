@@ -22,6 +22,7 @@
  *   rt_closest_hit_range_device  (an extension: the closest hit within a per-ray distance range, with its
  *                         distance and the reference's s, t; raytracing.cpp:106-149, :182)
  *   rt_occluded_range_device  (an extension: occlusion within a range, isShadow's rule or any opaque triangle)
+ *   rt_multi_hit_range_device  (an extension: the first k hits of each ray within a range, from one walk)
  *   rt_debug_trace       debug key 'd' (shoot + trace)     raytracing.cpp:493-510
  *                         (batched; also trace(o,d,lvl) at lvl 0, raytracing.h:30)
  *   rt_render_tile        the 'r'-key frame loop            main.cpp:340-411 (loop :355-395,
@@ -332,7 +333,9 @@ typedef struct {
 /* d_hit_out[i] (n x rt_hit, 16-byte aligned) = the lexicographic (distance, index) minimum over the in-range
  * accepted triangles, or {-1, +inf, 0, 0}; d_point_out (3n packed floats, may be NULL) = the intersection
  * point (:130) or (0,0,0). With both bounds NULL and flags 0, triangle and point are rt_intersect_mesh_device's
- * bits. tmin = nextafterf(previous distance, +inf) steps to the next surface along the ray.
+ * bits. tmin = nextafterf(previous distance, +inf) steps to the next distance along the ray; it skips every
+ * other accepted triangle at the previous distance (duplicated or coincident geometry, shared edges), which
+ * rt_multi_hit_range_device does not.
  * flags: RT_RANGE_TO_DEST. */
 int rt_closest_hit_range_device(rt_scene *scene, const void *d_origins, const void *d_dests, int32_t ray_stride,
                                 int32_t n, const void *d_count, const void *d_tmin, const void *d_tmax, uint32_t flags,
@@ -345,6 +348,26 @@ int rt_closest_hit_range_device(rt_scene *scene, const void *d_origins, const vo
 int rt_occluded_range_device(rt_scene *scene, const void *d_origins, const void *d_dests, int32_t ray_stride,
                              int32_t n, const void *d_count, const void *d_tmin, const void *d_tmax, uint32_t flags,
                              void *d_blocked_out, void *stream);
+/* The first k hits of each ray, from one walk. Accepted, distance, in range, the bounds, RT_RANGE_TO_DEST, the
+ * FLT_MAX clamp, empty ranges, rays, ray_stride, d_count, stream and the ordering against updates, rebuilds,
+ * rt_scene_set_mesh and rt_scene_destroy are exactly those of rt_closest_hit_range_device.
+ * d_hits_out (n x k rt_hit, ray-major, 16-byte aligned): with m the number of in-range accepted triangles of
+ * ray i, rows [i*k, i*k + min(m, k)) are those triangles' records in ascending lexicographic (distance, index)
+ * order, each with the distance, s, t bits rt_closest_hit_range_device gives for that triangle; the ray's
+ * other rows are the miss record {-1, +inf, 0, 0}. Triangles at one distance all appear, lowest index first:
+ * nothing is skipped as stepping by nextafterf does. With k = 1 and no flag, row i is
+ * rt_closest_hit_range_device's record bit for bit.
+ * d_nhits_out (n x int32, 4-byte aligned; may be NULL unless RT_MULTI_COUNT_ALL): min(m, k), or with
+ * RT_MULTI_COUNT_ALL m itself (so a caller sees that k truncated the list, or reads the crossing parity with
+ * k = 1); the hit rows are the same bytes either way. Rays at or past the live count are not written.
+ * flags: RT_RANGE_TO_DEST, RT_MULTI_COUNT_ALL. Errors as the ranged entries; in addition RT_E_ARG for k < 1 or
+ * k > RT_MULTI_HIT_MAX, d_hits_out NULL (n > 0) or not 16-byte aligned, d_nhits_out not 4-byte aligned,
+ * RT_MULTI_COUNT_ALL with a NULL d_nhits_out, n * k above INT32_MAX. */
+#define RT_MULTI_HIT_MAX   16
+#define RT_MULTI_COUNT_ALL (1u << 2)      /* d_nhits_out = all in-range accepted triangles, not min(m, k) */
+int rt_multi_hit_range_device(rt_scene *scene, const void *d_origins, const void *d_dests, int32_t ray_stride,
+                              int32_t n, const void *d_count, const void *d_tmin, const void *d_tmax, uint32_t flags,
+                              int32_t k, void *d_hits_out, void *d_nhits_out, void *stream);
 /* performRayTracing (raytracing.cpp:410-416) for rays in device memory: d_rgb_out[3*i..] (3n packed floats),
  * bit for bit rt_trace_rays' rgb_out. counts as in rt_trace_rays; non-NULL synchronises the stream. Uses
  * render pipeline 0's workspace (ordered against the frames that use it): returns after enqueueing when

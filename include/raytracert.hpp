@@ -207,6 +207,14 @@ class RayTracer {
         check(rt_occluded_range_device(scene_, d_origins, d_dests, ray_stride, n, d_count, d_tmin, d_tmax, flags, d_blocked_out,
                                        stream));
     }
+    // ... and the first k hits of each ray in that range from one walk (rt_multi_hit_range_device: d_hits_out
+    // n x k rt_hit, d_nhits_out n x int32 or null; flags RT_RANGE_TO_DEST / RT_MULTI_COUNT_ALL)
+    void multi_hit_range_device(const void *d_origins, const void *d_dests, int32_t ray_stride, int32_t n, const void *d_count,
+                                const void *d_tmin, const void *d_tmax, uint32_t flags, int32_t k, void *d_hits_out,
+                                void *d_nhits_out, void *stream) {
+        check(rt_multi_hit_range_device(scene_, d_origins, d_dests, ray_stride, n, d_count, d_tmin, d_tmax, flags, k, d_hits_out,
+                                        d_nhits_out, stream));
+    }
     void perform_ray_tracing_device(const void *d_origins, const void *d_dests, int32_t ray_stride, int32_t n, void *d_rgb_out,
                                     void *stream, uint64_t counts[3] = nullptr) {
         rt_params p = params();

@@ -438,7 +438,8 @@ class Scene:
         one (n, 4) int32 record tensor (rt_hit: a miss is -1, +inf, 0, 0), and with want_points also point[n, 3].
         out: that (>= n, 4) int32 record tensor to write into, or with want_points a (records, points) pair.
         With tmin = tmax = None and to_dest False, triangle and point are intersect_mesh_device's bits;
-        tmin = torch.nextafter(distance, inf) steps each ray to its next surface."""
+        tmin = torch.nextafter(distance, inf) steps each ray to its next distance; that skips every other accepted
+        triangle at the previous distance (duplicated or coincident geometry), which multi_hit_device does not."""
         import torch
         name = "closest_hit_device"
         n, stride = self._device_rays(name, "intersect_mesh", origins, dests)
@@ -459,6 +460,37 @@ class Scene:
         f = rec[:n].view(torch.float32)
         res = (rec[:n, 0], f[:, 1], f[:, 2:4])
         return res + (pts[:n],) if want_points else res
+
+    def multi_hit_device(self, origins, dests, k: int, tmin=None, tmax=None, to_dest: bool = False, count_all: bool = False,
+                         count=None, out=None, stream=None):
+        """rt_multi_hit_range_device: per ray, the first k (1.._capi.MULTI_HIT_MAX) accepted triangles whose distance
+        lies in [tmin, tmax), in ascending (distance, index) order, from one walk. Rays, bounds, to_dest, count and
+        stream as closest_hit_device. Returns (triangle[n, k] int32, distance[n, k] float32, st[n, k, 2] float32,
+        nhits[n] int32): the first three are views of one (n, k, 4) int32 record tensor whose rows past a ray's
+        hits are the miss record (-1, +inf, 0, 0); nhits is the number of rows that hold a hit, or with count_all
+        the number of in-range accepted triangles (which may exceed k). Triangles at one distance all appear,
+        lowest index first. out: a (records, nhits) pair to write into, (>= n, k, 4) int32 and (>= n,) int32."""
+        import torch
+        name = "multi_hit_device"
+        if not isinstance(k, int) or isinstance(k, bool) or k < 1 or k > _capi.MULTI_HIT_MAX:
+            raise ValueError(f"{name}: k must be an int in [1, {_capi.MULTI_HIT_MAX}], not {k!r}")
+        n, stride = self._device_rays(name, "intersect_mesh", origins, dests)
+        cnt = self._device_count(name, count)
+        lo, hi = self._device_bound(name, "tmin", tmin, n), self._device_bound(name, "tmax", tmax, n)
+        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
+            raise ValueError(f"{name}: out must be a (records, nhits) pair")
+        rec = self._device_out(name, None if out is None else out[0], n, torch.int32, (k, 4), 0, False)
+        if out is None and count is not None:          # entries a device count leaves unwritten: the miss record
+            rec[..., 0], rec[..., 1], rec[..., 2:] = -1, 0x7F800000, 0      # (device fills: no host copy)
+        if rec.data_ptr() % _capi.HIT_BYTES:
+            raise ValueError(f"{name}: the record tensor must be 16-byte aligned")
+        nh = self._device_out(name, None if out is None else out[1], n, torch.int32, (), 0, count is not None)
+        flags = (_capi.RANGE_TO_DEST if to_dest else 0) | (_capi.MULTI_COUNT_ALL if count_all else 0)
+        check(lib().rt_multi_hit_range_device(self._h, C.c_void_p(origins.data_ptr()), C.c_void_p(dests.data_ptr()), stride, n, cnt,
+                                              lo, hi, flags, k, C.c_void_p(rec.data_ptr()), C.c_void_p(nh.data_ptr()),
+                                              self._stream_ptr(stream)))
+        f = rec[:n].view(torch.float32)
+        return rec[:n, :, 0], f[:, :, 1], f[:, :, 2:4], nh[:n]
 
     def occluded_range_device(self, origins, dests, tmin=None, tmax=None, to_dest: bool = False, any_opaque: bool = False,
                               count=None, out=None, stream=None):

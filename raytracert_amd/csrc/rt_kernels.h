@@ -217,6 +217,13 @@ void launch_query_rays(const DevScene &s, bool occluded, const void *org, const 
 void launch_range_rays(const DevScene &s, bool occluded, bool any_opaque, bool to_dest, const void *org, const void *dst,
                        int32_t ray_stride, int32_t n, const int32_t *d_count, const float *d_tmin, const float *d_tmax, void *hit,
                        float *point, uint8_t *blocked, hipStream_t stream);
+// Multi-hit device query (rt_multi_hit_range_device): per ray the first k (1..16) in-range accepted triangles
+// in ascending (distance, index) order, from one walk. hits[n][k] 16-byte records, rows past a ray's list
+// the miss record; nhits[n] (may be null unless count_all) = the rows that hold a hit, or with count_all the
+// number of in-range accepted triangles. Bounds, to_dest and d_count as launch_range_rays.
+void launch_multi_rays(const DevScene &s, bool count_all, bool to_dest, const void *org, const void *dst, int32_t ray_stride,
+                       int32_t n, const int32_t *d_count, const float *d_tmin, const float *d_tmax, int32_t k, void *hits,
+                       int32_t *nhits, hipStream_t stream);
 // launch_gen_rays from the caller's device arrays in either layout (rt_trace_rays_device)
 void launch_gen_rays_device(const void *org, const void *dst, int32_t ray_stride, int32_t n, const DevWork &w,
                             hipStream_t stream);

@@ -163,11 +163,56 @@ constexpr int kTestStageFlops[kTestStages] = {14, 1, 23, 5, 9};
 // the upper bound; the lower one is the test below, made once the distance is known. kRangeOpaque (any-hit
 // only): the material is looked up once a triangle is accepted and in range, and a transparent one is
 // passed over (it does not end the walk). kRangeNone is every walk there was before: rg is never read.
-enum : int { kRangeNone = 0, kRangeBounded = 1, kRangeOpaque = 2 };
+// kRangeMulti / kRangeMultiAll (rt_multi_hit_range_device, closest-hit walks only): the k smallest
+// (distance, index) keys of the in-range accepted triangles, kept in rg.multi (MultiList, below).
+enum : int { kRangeNone = 0, kRangeBounded = 1, kRangeOpaque = 2, kRangeMulti = 3, kRangeMultiAll = 4 };
+constexpr bool range_multi(int kind) { return kind == kRangeMulti || kind == kRangeMultiAll; }
+__device__ __forceinline__ unsigned long long hit_key(float best, int bidx);
+
+// One lane's list of its ray's k smallest keys so far, ascending, in LDS ([slot][block lane], as LaneStack;
+// dynamic indexing of a per-lane array would go to scratch). k is the launch's, so wave-uniform. hit_key
+// orders (distance, index) as an unsigned 64-bit integer: accepted distances are non-negative floats (a NaN
+// fails dist >= tmin), and no key comes twice, since a walk meets each triangle at most once (every triangle
+// is in the always list or in exactly one leaf, rt_scene_bvh_validate).
+// The walk's own best / bidx are the admission bound: (tmax, -1) while the list holds fewer than k keys,
+// so the update test of test_triangle admits exactly the in-range triangles, then the k-th key, so it
+// admits exactly the keys below that one. kAll (RT_MULTI_COUNT_ALL): the walk's best stays tmax, every
+// in-range accepted triangle is counted, and the list keeps its k-th key as a bound of its own (kd, ki).
+struct MultiList {
+    unsigned long long *keys;   // this lane's slot 0; slot i is keys[i * width]
+    int width, k;
+    int cnt = 0, total = 0;     // keys held; kAll: in-range accepted triangles met
+    float kd = 0.0f;            // kAll: the list's admission bound
+    int ki = -1;
+    template <bool kAll>
+    __device__ __forceinline__ void admit(float dist, int t, float &best, int &bidx) {
+        if (kAll) {
+            ++total;
+            if (!(dist < kd || (dist == kd && t < ki))) return;
+        }
+        const unsigned long long key = hit_key(dist, t);
+        int i = min(cnt, k - 1);   // the slot that opens: the end of a list not yet full, else the last (its key drops out)
+        while (i > 0) {            // compare-shift
+            const unsigned long long prev = keys[(i - 1) * width];
+            if (prev < key) break;
+            keys[i * width] = prev;
+            --i;
+        }
+        keys[i * width] = key;
+        cnt = min(cnt + 1, k);
+        if (cnt == k) {            // full: from now on only keys below the k-th can be among the k smallest
+            const unsigned long long last = keys[(k - 1) * width];
+            const float d = __uint_as_float(static_cast<uint32_t>(last >> 32));
+            if (kAll) { kd = d; ki = static_cast<int>(static_cast<uint32_t>(last)); }
+            else { best = d; bidx = static_cast<int>(static_cast<uint32_t>(last)); }
+        }
+    }
+};
 struct RayRange {
     float tmin = 0.0f, tmax = FLT_MAX;
     const uint32_t *tri_mat = nullptr;      // kRangeOpaque only
     const DevMaterial *mats = nullptr;
+    MultiList *multi = nullptr;             // kRangeMulti / kRangeMultiAll only
 };
 template <bool kAnyHit, bool kLex = false, bool kSignFirst = false, bool kStages = false, int kRange = kRangeNone>
 __device__ __forceinline__ void test_triangle(const TriRec &T, int t, V3 o, V3 dir, float &best, int &bidx, V3 &bI,
@@ -198,6 +243,7 @@ __device__ __forceinline__ void test_triangle(const TriRec &T, int t, V3 o, V3 d
     if (kRange != kRangeNone && !(dist >= rg.tmin)) return;
     if (dist < best || (kLex && dist == best && t < bidx)) {                  // :183
         if (kRange == kRangeOpaque && rg.mats[rg.tri_mat[t]].transparent) return;
+        if (range_multi(kRange)) { rg.multi->admit<kRange == kRangeMultiAll>(dist, t, best, bidx); return; }
         best = dist; bidx = t; bI = I;
         if (kAnyHit) done = true;
     }
@@ -556,6 +602,14 @@ __device__ __forceinline__ int32_t node4_next(const Ray4 &R, const Node4Rows &nd
             stack.lds[(sp + 1) * stack.width + lane] = nh == 4 ? rc[2] : rc[1];
             stack.lds[(sp + 2) * stack.width + lane] = rc[1];
             sp += max(nh - 1, 0);
+        } else if (range_multi(kRange)) {
+            // The wanted children after the first, by their number. With a single wanted child tc[] is not
+            // sorted (only rc[0] was set above), so the pushes by tc[k] below also push that child when it
+            // stood in slot 1..3, and its subtree is walked twice. A (distance, index) minimum or an any-hit
+            // verdict is the same for that; a list or a count of hits is not.
+            if (nh > 3) stack.push(sp, rc[3]);
+            if (nh > 2) stack.push(sp, rc[2]);
+            if (nh > 1) stack.push(sp, rc[1]);
         } else {
             if (tc[3] != INFINITY) stack.push(sp, rc[3]);
             if (tc[2] != INFINITY) stack.push(sp, rc[2]);
@@ -1618,6 +1672,109 @@ __global__ __launch_bounds__(kBlock) void k_range_rays(const TriRec *__restrict_
     closest_hit_loop<range_any_hit(kMode), range_kind(kMode)>(tris, nt, o, dir, walk, bidx, bI, rg);
     if (!walk) { bidx = -1; bI = mk(0, 0, 0); }
     if (active) store_range<kMode>(tris, tri_mat, mats, j, bidx, bI, o, dir, q.hit, q.point, q.blocked);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Multi-hit device query (rt_multi_hit_range_device): per ray the first k in-range accepted triangles in
+// ascending (distance, index) order, from one walk (kRangeMulti; MultiList states the bound the walk culls
+// by). The launch shape is the ranged kernels'; the dynamic LDS holds the traversal stack's part and then
+// the lists, [k][block lanes] keys. Exactness: bvh.cpp's argument needs only that no triangle at a distance
+// above best can be part of the answer. With a full list a triangle beyond the k-th key is not among the k
+// smallest; with a list that is not full best is tmax and such a triangle is out of range. So the walk skips
+// only subtrees that cannot contribute, every insertion keeps the k smallest keys met so far, and the result
+// is the k smallest keys of the in-range set whatever the visiting order. kCountAll (RT_MULTI_COUNT_ALL):
+// best stays tmax for the cull, as in the ranged any-hit walk, so the whole range is walked and every
+// in-range accepted triangle is counted once.
+// After the walk each kept triangle's record is recomputed (hit_record, as the closest-record kernel does)
+// and stored as one 16-byte row; rows past the list are the miss record.
+// ---------------------------------------------------------------------------------------------
+struct MultiQuery {
+    const float *tmin, *tmax;   // per ray, or null
+    int32_t to_dest, k;
+    int4 *hit;                  // [n][k] records
+    int32_t *nhits;             // [n], or null
+};
+
+template <bool kCountAll>
+__device__ __forceinline__ void store_multi(const TriRec *__restrict__ tris, const MultiList &ml, int j, V3 o, V3 dir,
+                                            const MultiQuery &q) {
+    int4 *__restrict__ row = q.hit + static_cast<size_t>(j) * static_cast<size_t>(ml.k);
+    for (int i = 0; i < ml.k; ++i) {
+        int4 rec = make_int4(-1, as_int(INFINITY), 0, 0);
+        if (i < ml.cnt) {
+            const int idx = static_cast<int>(static_cast<uint32_t>(ml.keys[i * ml.width]));
+            rec = hit_record(tris[idx], idx, o, dir);
+        }
+        row[i] = rec;                                                              // one 16-byte store
+    }
+    if (q.nhits) q.nhits[j] = kCountAll ? ml.total : ml.cnt;
+}
+
+template <int W, int kStride, bool kCount, bool kCountAll>
+__global__ __launch_bounds__(kBvhBlock) void k_bvh_multi_rays(const DevScene sc, const void *__restrict__ org,
+                                                              const void *__restrict__ dst, int n,
+                                                              const int32_t *__restrict__ d_count, const MultiQuery q) {
+    extern __shared__ int32_t lds_stack[];
+    const LaneStack stack = lane_stack(sc, lds_stack);
+    unsigned long long *const lists = reinterpret_cast<unsigned long long *>(lds_stack + max(sc.lds_stack, 1) * kBvhBlock);
+    WorkTally<kCount> wt;
+    drive_queries(live_rays(d_count, n), 0, nullptr, [&](int j, int end) {
+        const bool active = j < end;
+        V3 o = mk(0, 0, 0), dir = mk(0, 0, 0);
+        RayRange rg;
+        MultiList ml;
+        ml.keys = lists + threadIdx.x;
+        ml.width = kBvhBlock;
+        ml.k = q.k;
+        rg.multi = &ml;
+        bool walk = false;
+        if (active) {
+            o = load_ray_point<kStride>(org, j);
+            dir = sub(load_ray_point<kStride>(dst, j), o);                          // :111
+            walk = load_range(q.tmin, q.tmax, q.to_dest != 0, j, dir, rg);
+        }
+        ml.kd = rg.tmax;
+        int bidx = -1;
+        V3 bI = mk(0, 0, 0);
+        wt.begin();
+        bvh_query_w<false, W, false, kCountAll ? kRangeMultiAll : kRangeMulti>(sc, o, dir, walk, bidx, bI, stack, wt.tests, wt.visits, rg);
+        wt.end();
+        if (!walk) { ml.cnt = 0; ml.total = 0; }   // (an empty range: k miss rows and a count of 0)
+        if (active) store_multi<kCountAll>(sc.tris, ml, j, o, dir, q);
+    });
+    wt.flush(sc.work);
+}
+
+// The same over every triangle in index order (RT_ACCEL_BRUTE_FORCE, or no tree could be built).
+template <int kStride, bool kCountAll>
+__global__ __launch_bounds__(kBlock) void k_multi_rays(const TriRec *__restrict__ tris, int nt, const void *__restrict__ org,
+                                                       const void *__restrict__ dst, int n, const int32_t *__restrict__ d_count,
+                                                       const MultiQuery q) {
+    extern __shared__ int32_t lds_stack[];   // the lists alone
+    const int live = live_rays(d_count, n);
+    const int64_t base = static_cast<int64_t>(blockIdx.x) * kBlock;
+    if (base >= live) return;
+    const bool active = base + threadIdx.x < live;
+    const int j = active ? static_cast<int>(base + threadIdx.x) : 0;
+    V3 o = mk(0, 0, 0), dir = mk(0, 0, 0);
+    RayRange rg;
+    MultiList ml;
+    ml.keys = reinterpret_cast<unsigned long long *>(lds_stack) + threadIdx.x;
+    ml.width = kBlock;
+    ml.k = q.k;
+    rg.multi = &ml;
+    bool walk = false;
+    if (active) {
+        o = load_ray_point<kStride>(org, j);
+        dir = sub(load_ray_point<kStride>(dst, j), o);
+        walk = load_range(q.tmin, q.tmax, q.to_dest != 0, j, dir, rg);
+    }
+    ml.kd = rg.tmax;
+    int bidx = -1;
+    V3 bI = mk(0, 0, 0);
+    closest_hit_loop<false, kCountAll ? kRangeMultiAll : kRangeMulti>(tris, nt, o, dir, walk, bidx, bI, rg);
+    if (!walk) { ml.cnt = 0; ml.total = 0; }
+    if (active) store_multi<kCountAll>(tris, ml, j, o, dir, q);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3983,6 +4140,8 @@ void launch_gen_rays(const float4 *org, const float4 *dst, int32_t n, const DevW
 inline size_t bvh_lds(const DevScene &s, int lanes = kBvhBlock) {
     return sizeof(int32_t) * lanes * static_cast<size_t>(std::max(s.lds_stack, 1));
 }
+// LDS of the multi-hit kernels' lists: k 64-bit keys per lane
+inline size_t multi_lds(int k, int lanes) { return sizeof(unsigned long long) * lanes * static_cast<size_t>(k); }
 inline DevScene for_width(DevScene s, int) { return s; }
 
 // Grid cap of the per-step BVH kernels (resident size at 7 waves per SIMD: a grid-stride walk).
@@ -4370,6 +4529,39 @@ void launch_range_rays(const DevScene &s, bool occluded, bool any_opaque, bool t
     else if (!s.any_transparent) launch_range_stride<kRangeOccludedAny>(s, org, dst, ray_stride, n, d_count, q, stream);   // either rule
     else if (any_opaque) launch_range_stride<kRangeOccludedAnyOpaque>(s, org, dst, ray_stride, n, d_count, q, stream);
     else launch_range_stride<kRangeOccludedClosest>(s, org, dst, ray_stride, n, d_count, q, stream);
+}
+
+namespace {
+template <int kStride, bool kCountAll>
+void launch_multi_mode(const DevScene &s0, const void *org, const void *dst, int32_t n, const int32_t *d_count, const MultiQuery &q,
+                       hipStream_t stream) {
+    if (s0.use_bvh) {   // launch_range_mode's shape; the lists' LDS follows the stack's
+        const int W = s0.bvh_width == 4 ? 4 : 2;
+        const DevScene s = for_width(s0, W);
+        auto k = W == 4 ? (s.work ? k_bvh_multi_rays<4, kStride, true, kCountAll> : k_bvh_multi_rays<4, kStride, false, kCountAll>)
+                        : (s.work ? k_bvh_multi_rays<2, kStride, true, kCountAll> : k_bvh_multi_rays<2, kStride, false, kCountAll>);
+        hipLaunchKernelGGL(k, dim3(grid_bvh(n, s.bvh_grid)), dim3(kBvhBlock), bvh_lds(s) + multi_lds(q.k, kBvhBlock), stream, s, org, dst,
+                           n, d_count, q);
+        return;
+    }
+    hipLaunchKernelGGL((k_multi_rays<kStride, kCountAll>), dim3(grid_for(n)), dim3(kBlock), multi_lds(q.k, kBlock), stream, s0.tris,
+                       s0.nt, org, dst, n, d_count, q);
+}
+}  // namespace
+
+void launch_multi_rays(const DevScene &s, bool count_all, bool to_dest, const void *org, const void *dst, int32_t ray_stride,
+                       int32_t n, const int32_t *d_count, const float *d_tmin, const float *d_tmax, int32_t k, void *hits,
+                       int32_t *nhits, hipStream_t stream) {
+    if (n <= 0) return;
+    const MultiQuery q{d_tmin, d_tmax, to_dest ? 1 : 0, k, static_cast<int4 *>(hits), nhits};
+    const bool wide = ray_stride == 4;
+    if (count_all) {
+        if (wide) launch_multi_mode<4, true>(s, org, dst, n, d_count, q, stream);
+        else launch_multi_mode<3, true>(s, org, dst, n, d_count, q, stream);
+    } else {
+        if (wide) launch_multi_mode<4, false>(s, org, dst, n, d_count, q, stream);
+        else launch_multi_mode<3, false>(s, org, dst, n, d_count, q, stream);
+    }
 }
 
 void launch_gen_rays_device(const void *org, const void *dst, int32_t ray_stride, int32_t n, const DevWork &w, hipStream_t stream) {
