@@ -23,6 +23,7 @@
  *                         distance and the reference's s, t; raytracing.cpp:106-149, :182)
  *   rt_occluded_range_device  (an extension: occlusion within a range, isShadow's rule or any opaque triangle)
  *   rt_multi_hit_range_device  (an extension: the first k hits of each ray within a range, from one walk)
+ *   rt_closest_point_device  (an extension: the nearest point of the mesh to each query point)
  *   rt_debug_trace       debug key 'd' (shoot + trace)     raytracing.cpp:493-510
  *                         (batched; also trace(o,d,lvl) at lvl 0, raytracing.h:30)
  *   rt_render_tile        the 'r'-key frame loop            main.cpp:340-411 (loop :355-395,
@@ -368,6 +369,52 @@ int rt_occluded_range_device(rt_scene *scene, const void *d_origins, const void 
 int rt_multi_hit_range_device(rt_scene *scene, const void *d_origins, const void *d_dests, int32_t ray_stride,
                               int32_t n, const void *d_count, const void *d_tmin, const void *d_tmax, uint32_t flags,
                               int32_t k, void *d_hits_out, void *d_nhits_out, void *stream);
+/* The nearest point of the mesh to each query point (an extension: no ray is involved).
+ * d_points: n points, float32 in device memory on the scene's device, point_stride RT_RAYS_PACKED or
+ * RT_RAYS_PADDED (w ignored, 16-byte aligned). d_count, stream and the ordering against updates, rebuilds,
+ * rt_scene_set_mesh and rt_scene_destroy are exactly those of rt_closest_hit_range_device; rows at or past the
+ * live count are neither read nor written.
+ * d_hit_out (n x rt_hit, 16-byte aligned): {triangle, distance, s, t} with the closest point
+ * V0 + s (V1 - V0) + t (V2 - V0); a miss is {-1, +inf, 0, 0}. d_point_out (3n packed floats, may be NULL): the
+ * closest point c below, or (0,0,0) on a miss. d_rmax (n floats, 4-byte aligned, may be NULL): a search radius
+ * per point. flags must be 0 (RT_E_ARG otherwise). Errors as the ranged entries, in their order.
+ *
+ * The definition. Everything is binary32 without contraction, a dot product is (ax bx + ay by) + az bz,
+ * division and sqrtf are correctly rounded. With T0 = V0, u = V1 - V0, v = V2 - V0, uu = dot(u, u),
+ * uv = dot(u, v), vv = dot(v, v) (the triangle's record), a triangle is a candidate unless its normal u x v is
+ * (0,0,0): the class rt_bvh_acceptance_box reports as 2, the triangles no ray entry ever returns. For a
+ * candidate and a point p, with w = p - T0:
+ *   d1 = dot(u, w)      d2 = dot(v, w)
+ *   d3 = d1 - uu        d4 = d2 - uv
+ *   d5 = d1 - uv        d6 = d2 - vv
+ *   vc = d1 d4 - d3 d2  vb = d5 d2 - d1 d6  va = d3 d6 - d5 d4
+ *   the first that holds:
+ *     d1 <= 0 && d2 <= 0                        : s = 0, t = 0                     (vertex 0)
+ *     d3 >= 0 && d4 <= d3                       : s = 1, t = 0                     (vertex 1)
+ *     vc <= 0 && d1 >= 0 && d3 <= 0             : s = d1 / (d1 - d3), t = 0        (edge 0-1)
+ *     d6 >= 0 && d5 <= d6                       : s = 0, t = 1                     (vertex 2)
+ *     vb <= 0 && d2 >= 0 && d6 <= 0             : s = 0, t = d2 / (d2 - d6)        (edge 0-2)
+ *     va <= 0 && d4 - d3 >= 0 && d5 - d6 >= 0   : t = (d4 - d3) / ((d4 - d3) + (d5 - d6)), s = 1 - t   (edge 1-2)
+ *     otherwise                                 : q = 1 / ((va + vb) + vc), s = vb q, t = vc q, then
+ *                                                 if (s < 0) s = 0; if (s > 1) s = 1; m = 1 - s;
+ *                                                 if (t < 0) t = 0; if (t > m) t = m            (interior)
+ *   c = (T0 + s u) + t v per component     r = p - c     dist2 = dot(r, r)
+ * (The interior's four compares keep s, t inside the triangle when va, vb, vc are rounding noise, as they are far
+ * from a small triangle; a NaN passes through them unchanged.)
+ * The answer for point i is the lexicographic (dist2, triangle index) minimum over the candidates with
+ * dist2 < bound_i; bound_i is +inf when d_rmax is NULL, else rmax_i * rmax_i rounded to float when rmax_i > 0; a
+ * NaN, zero or negative radius is an empty search, a miss. The record's distance is sqrtf(dist2).
+ * Consequences: a NaN in the arithmetic falls through to the interior case and gives a NaN dist2, which never
+ * wins; a point with a NaN or infinite component is a miss; so is a point so far away that dist2 overflows.
+ * The result does not depend on the acceleration structure: the tree walk returns the bytes of the loop over
+ * every triangle. */
+int rt_closest_point_device(rt_scene *scene, const void *d_points, int32_t point_stride, int32_t n,
+                            const void *d_count, const void *d_rmax, uint32_t flags,
+                            void *d_hit_out, void *d_point_out, void *stream);
+/* The same for host arrays (points 3n packed floats, rmax n floats or NULL, point_out 3n floats or NULL):
+ * copy in, the same launch, copy out, synchronise. The same bits. */
+int rt_closest_point(rt_scene *scene, const float *points, int32_t n, const float *rmax,
+                     rt_hit *hit_out, float *point_out);
 /* performRayTracing (raytracing.cpp:410-416) for rays in device memory: d_rgb_out[3*i..] (3n packed floats),
  * bit for bit rt_trace_rays' rgb_out. counts as in rt_trace_rays; non-NULL synchronises the stream. Uses
  * render pipeline 0's workspace (ordered against the frames that use it): returns after enqueueing when

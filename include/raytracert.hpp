@@ -215,6 +215,12 @@ class RayTracer {
         check(rt_multi_hit_range_device(scene_, d_origins, d_dests, ray_stride, n, d_count, d_tmin, d_tmax, flags, k, d_hits_out,
                                         d_nhits_out, stream));
     }
+    // the nearest point of the mesh to each query point (rt_closest_point_device: d_hit_out n x rt_hit, d_point_out
+    // 3n floats or null, d_rmax n search radii or null; flags 0)
+    void closest_point_device(const void *d_points, int32_t point_stride, int32_t n, const void *d_count, const void *d_rmax,
+                              uint32_t flags, void *d_hit_out, void *d_point_out, void *stream) {
+        check(rt_closest_point_device(scene_, d_points, point_stride, n, d_count, d_rmax, flags, d_hit_out, d_point_out, stream));
+    }
     void perform_ray_tracing_device(const void *d_origins, const void *d_dests, int32_t ray_stride, int32_t n, void *d_rgb_out,
                                     void *stream, uint64_t counts[3] = nullptr) {
         rt_params p = params();

@@ -138,6 +138,8 @@ _SIGNATURES = {
     "rt_closest_hit_range_device": ([_VP, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_uint32, _VP, _VP, _VP], C.c_int),
     "rt_occluded_range_device": ([_VP, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_uint32, _VP, _VP], C.c_int),
     "rt_multi_hit_range_device": ([_VP, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_uint32, C.c_int32, _VP, _VP, _VP], C.c_int),
+    "rt_closest_point_device": ([_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, C.c_uint32, _VP, _VP, _VP], C.c_int),
+    "rt_closest_point": ([_VP, _VP, C.c_int32, _VP, _VP, _VP], C.c_int),
     "rt_trace_rays_device": ([_VP, C.POINTER(RtParams), _VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP], C.c_int),
     "rt_debug_trace": ([_VP, C.POINTER(RtParams), _VP, _VP, _VP, C.c_int32, C.POINTER(C.c_int32), _VP], C.c_int),
     "rt_render_tile": ([_VP, C.POINTER(RtParams), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP], C.c_int),

@@ -335,10 +335,10 @@ class Scene:
         return rgb, counts
 
     # -- device-resident queries (rays and results are torch CUDA tensors; stream-ordered, no host sync) ----
-    def _device_rays(self, name: str, host_method: str, origins, dests):
+    def _device_rays(self, name: str, host_method: str, origins, dests, names=("origins", "dests")):
         """Checks before anything touches a device: (n, ray_stride) of two CUDA float32 ray tensors."""
         import torch
-        for what, t in (("origins", origins), ("dests", dests)):
+        for what, t in zip(names, (origins, dests)):
             if not isinstance(t, torch.Tensor):
                 raise ValueError(f"{name}: {what} must be a CUDA torch tensor (host arrays go through {host_method})")
             if t.dtype != torch.float32:
@@ -491,6 +491,50 @@ class Scene:
                                               self._stream_ptr(stream)))
         f = rec[:n].view(torch.float32)
         return rec[:n, :, 0], f[:, :, 1], f[:, :, 2:4], nh[:n]
+
+    def closest_point_device(self, points, rmax=None, count=None, out=None, want_points: bool = False, stream=None):
+        """rt_closest_point_device: per query point, the nearest point of the mesh (include/raytracert.h states the
+        arithmetic). points: a contiguous CUDA float32 tensor on the scene's device, (n, 3) or (n, 4) (w ignored);
+        rmax: an optional CUDA float32 tensor of n search radii (a NaN, zero or negative radius is a miss); count
+        and stream as intersect_mesh_device. Returns (triangle[n] int32, distance[n] float32, st[n, 2] float32),
+        views of one (n, 4) int32 record tensor (rt_hit: a miss is -1, +inf, 0, 0), and with want_points also
+        point[n, 3], the closest point V0 + s (V1 - V0) + t (V2 - V0) or (0, 0, 0). out: that (>= n, 4) int32
+        record tensor to write into, or with want_points a (records, points) pair."""
+        import torch
+        name = "closest_point_device"
+        n, stride = self._device_rays(name, "closest_point", points, points, ("points", "points"))
+        cnt = self._device_count(name, count)
+        rad = self._device_bound(name, "rmax", rmax, n)
+        if want_points and out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
+            raise ValueError(f"{name}: with want_points, out must be a (records, points) pair")
+        out_rec = out[0] if (want_points and out is not None) else out
+        rec = self._device_out(name, out_rec, n, torch.int32, (4,), 0, False)
+        if out_rec is None and count is not None:      # entries a device count leaves unwritten: the miss record
+            rec[:, 0], rec[:, 1], rec[:, 2:] = -1, 0x7F800000, 0      # (device fills: no host copy)
+        if rec.data_ptr() % _capi.HIT_BYTES:
+            raise ValueError(f"{name}: the record tensor must be 16-byte aligned")
+        pts = self._device_out(name, None if out is None else out[1], n, torch.float32, (3,), 0.0, count is not None) if want_points else None
+        check(lib().rt_closest_point_device(self._h, C.c_void_p(points.data_ptr()), stride, n, cnt, rad, 0, C.c_void_p(rec.data_ptr()),
+                                            None if pts is None else C.c_void_p(pts.data_ptr()), self._stream_ptr(stream)))
+        f = rec[:n].view(torch.float32)
+        res = (rec[:n, 0], f[:, 1], f[:, 2:4])
+        return res + (pts[:n],) if want_points else res
+
+    def closest_point(self, points, rmax=None):
+        """rt_closest_point for numpy arrays: returns (triangle[n] int32, distance[n] float32, st[n, 2] float32,
+        point[n, 3] float32), closest_point_device's bits. rmax: optional n search radii."""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n = len(p)
+        r = None
+        if rmax is not None:
+            r = np.ascontiguousarray(rmax, np.float32).reshape(-1)
+            if len(r) != n:
+                raise ValueError(f"closest_point: rmax has {len(r)} elements for {n} points")
+        rec = np.zeros((n, 4), np.int32)
+        pts = np.zeros((n, 3), np.float32)
+        check(lib().rt_closest_point(self._h, _ptr(p), n, None if r is None else _ptr(r), _ptr(rec), _ptr(pts)))
+        f = rec.view(np.float32)
+        return rec[:, 0], f[:, 1], f[:, 2:4], pts
 
     def occluded_range_device(self, origins, dests, tmin=None, tmax=None, to_dest: bool = False, any_opaque: bool = False,
                               count=None, out=None, stream=None):

@@ -224,6 +224,13 @@ void launch_range_rays(const DevScene &s, bool occluded, bool any_opaque, bool t
 void launch_multi_rays(const DevScene &s, bool count_all, bool to_dest, const void *org, const void *dst, int32_t ray_stride,
                        int32_t n, const int32_t *d_count, const float *d_tmin, const float *d_tmax, int32_t k, void *hits,
                        int32_t *nhits, hipStream_t stream);
+// Closest-point device query (rt_closest_point_device): per point at pts (point_stride 3 or 4, as the rays)
+// the nearest point of the mesh: hit[n] 16-byte records {triangle, distance, s, t} (a miss -1, +inf, 0, 0)
+// and, when point is not null, point[3 n]. d_rmax (n floats or null): the search radius per point. d_count
+// as launch_query_rays. The tree walk (k_bvh_point_query) and the loop over every triangle (k_point_query)
+// give the same bytes.
+void launch_point_query(const DevScene &s, const void *pts, int32_t point_stride, int32_t n, const int32_t *d_count,
+                        const float *d_rmax, void *hit, float *point, hipStream_t stream);
 // launch_gen_rays from the caller's device arrays in either layout (rt_trace_rays_device)
 void launch_gen_rays_device(const void *org, const void *dst, int32_t ray_stride, int32_t n, const DevWork &w,
                             hipStream_t stream);

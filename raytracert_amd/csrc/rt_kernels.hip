@@ -1778,6 +1778,240 @@ __global__ __launch_bounds__(kBlock) void k_multi_rays(const TriRec *__restrict_
 }
 
 // ---------------------------------------------------------------------------------------------
+// Closest-point queries (rt_closest_point_device): per query point the nearest point of the mesh, as the
+// rt_hit record {triangle, distance, s, t} of the lexicographic (dist2, index) minimum over the candidate
+// triangles (record normal not (0,0,0)) with dist2 below the point's bound (include/raytracert.h states the
+// arithmetic; closest_on_triangle is that statement op for op). k_point_query evaluates every triangle in
+// index order; k_bvh_point_query walks the tree nearest child first and culls by the squared distance from
+// the point to a child's box.
+//
+// Exactness (DESIGN.md §7 "Closest-point queries" has the argument in full): the boxes of the tree contain
+// the vertices of every tree triangle, and every branch of closest_on_triangle leaves s, t in [0, 1] with
+// s + t <= 1 + 2^-24, so the computed c lies within 15 * 2^-24 * m1 (m1 = scene_m1) of a point of the
+// triangle, and sqrt(dist2) >= D - 19 * 2^-24 * M for D the distance from p to the box and M = m1 + |p|_1,
+// while sqrt(db2) <= D (1 + 3 * 2^-24). A child is skipped only when its computed box distance db2 exceeds
+//     cull2 = h h (1 + 1e-6),  h = (sqrtf(best2) + 32 * 2^-24 * M) (1 + 1e-6)
+// (point_cull; the two factors cover the roundings of db2, of h and of the square), which puts every
+// candidate below it at a dist2 strictly above best2: it can neither beat best nor tie with it. best2 starts
+// at the point's bound (nothing at or above it is an answer) and cull2 is refreshed only when best improves,
+// so a node visit costs no sqrtf. The result is the brute-force loop's whatever the tree and the visiting order.
+// A point with a NaN or infinite component, or an empty search (a NaN, zero or negative radius), is a miss by
+// the definition and takes no part in the walk.
+// ---------------------------------------------------------------------------------------------
+struct PointQuery {
+    const float *rmax;          // per point, or null
+    int4 *hit;                  // the records
+    float *point;               // may be null
+};
+
+// The point of triangle T nearest to p (the header's sequence, binary32, one rounding per operation):
+// returns dist2 and sets s, t and c = (T0 + s u) + t v.
+__device__ __forceinline__ float closest_on_triangle(const TriRec &T, V3 p, float &s, float &t, V3 &c) {
+    const V3 u = mk(T.u[0], T.u[1], T.u[2]), v = mk(T.v[0], T.v[1], T.v[2]);
+    const V3 w = mk(p.x - T.t0[0], p.y - T.t0[1], p.z - T.t0[2]);
+    const float d1 = dot(u, w), d2 = dot(v, w);
+    const float d3 = d1 - T.uu, d4 = d2 - T.uv;
+    const float d5 = d1 - T.uv, d6 = d2 - T.vv;
+    const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+    if (d1 <= 0.0f && d2 <= 0.0f) {                                    // vertex 0
+        s = 0.0f; t = 0.0f;
+    } else if (d3 >= 0.0f && d4 <= d3) {                               // vertex 1
+        s = 1.0f; t = 0.0f;
+    } else if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) {               // edge 0-1
+        s = d1 / (d1 - d3); t = 0.0f;
+    } else if (d6 >= 0.0f && d5 <= d6) {                               // vertex 2
+        s = 0.0f; t = 1.0f;
+    } else if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) {               // edge 0-2
+        s = 0.0f; t = d2 / (d2 - d6);
+    } else if (va <= 0.0f && d4 - d3 >= 0.0f && d5 - d6 >= 0.0f) {     // edge 1-2
+        t = (d4 - d3) / ((d4 - d3) + (d5 - d6)); s = 1.0f - t;
+    } else {                                                           // interior
+        const float q = 1.0f / ((va + vb) + vc);
+        s = vb * q; t = vc * q;
+        // clamped into the triangle by compares (a NaN stays a NaN): far from a small triangle va, vb, vc are
+        // rounding noise and their quotients anything
+        s = s < 0.0f ? 0.0f : s; s = s > 1.0f ? 1.0f : s;
+        const float m = 1.0f - s;
+        t = t < 0.0f ? 0.0f : t; t = t > m ? m : t;
+    }
+    c = mk((T.t0[0] + s * u.x) + t * v.x, (T.t0[1] + s * u.y) + t * v.y, (T.t0[2] + s * u.z) + t * v.z);
+    const V3 r = sub(p, c);
+    return dot(r, r);
+}
+
+__device__ __forceinline__ bool point_candidate(const TriRec &T) { return !(T.n[0] == 0.0f && T.n[1] == 0.0f && T.n[2] == 0.0f); }
+
+// One candidate against the best so far: the lexicographic (dist2, index) order once something is found,
+// dist2 < bound before (bidx < 0: best2 is the bound). true when best changed.
+__device__ __forceinline__ bool point_eval(const TriRec &T, int idx, V3 p, float &best2, int &bidx) {
+    if (!point_candidate(T)) return false;
+    float s, t;
+    V3 c;
+    const float d2 = closest_on_triangle(T, p, s, t, c);
+    if (d2 < best2 || (d2 == best2 && bidx >= 0 && idx < bidx)) {
+        best2 = d2;
+        bidx = idx;
+        return true;
+    }
+    return false;
+}
+
+// The point's search bound and whether it searches at all.
+__device__ __forceinline__ bool load_point_bound(const float *__restrict__ d_rmax, int j, V3 p, float &bound) {
+    bound = INFINITY;
+    bool walk = fabsf(p.x) < INFINITY && fabsf(p.y) < INFINITY && fabsf(p.z) < INFINITY;   // (a NaN compares false)
+    if (d_rmax) {
+        const float r = d_rmax[j];
+        walk = walk && r > 0.0f;
+        bound = r * r;
+    }
+    return walk;
+}
+
+__device__ __forceinline__ void store_point(const TriRec *__restrict__ tris, int j, int bidx, V3 p, const PointQuery &q) {
+    int4 rec = make_int4(-1, as_int(INFINITY), 0, 0);
+    V3 c = mk(0, 0, 0);
+    if (bidx >= 0) {   // recomputed from the scene's record, the bytes of the copy the walk read (as hit_record)
+        float s, t;
+        const float d2 = closest_on_triangle(tris[bidx], p, s, t, c);
+        rec = make_int4(bidx, as_int(sqrtf(d2)), as_int(s), as_int(t));
+    }
+    q.hit[j] = rec;                                                                // one 16-byte store
+    if (q.point) reinterpret_cast<V3 *>(q.point)[j] = c;
+}
+
+// cull2 of the comment above; slack = 32 * 2^-24 * M
+__device__ __forceinline__ float point_cull(float best2, float slack) {
+    const float h = (sqrtf(best2) + slack) * 1.000001f;
+    return (h * h) * 1.000001f;
+}
+
+__device__ __forceinline__ float box_dist2(V3 p, float lx, float ly, float lz, float hx, float hy, float hz) {
+    const float ex = fmaxf(fmaxf(lx - p.x, p.x - hx), 0.0f);
+    const float ey = fmaxf(fmaxf(ly - p.y, p.y - hy), 0.0f);
+    const float ez = fmaxf(fmaxf(lz - p.z, p.z - hz), 0.0f);
+    return (ex * ex + ey * ey) + ez * ez;
+}
+
+template <int W>
+__device__ __forceinline__ void bvh_point_walk(const DevScene &sc, V3 p, bool walk, float &best2, int &bidx,
+                                               const LaneStack &stack, unsigned &tests, unsigned &visits) {
+    // the always list: wave-uniform records, every lane
+    for (int i = 0; i < sc.n_always; ++i) point_eval(sc.always_recs[i], static_cast<int>(sc.always[i]), p, best2, bidx);
+    tests += static_cast<unsigned>(max(sc.n_always, 0));
+    if (!walk) return;
+    const float slack = 32.0f * 5.9604645e-08f * ((fabsf(p.x) + fabsf(p.y) + fabsf(p.z)) + sc.scene_m1);
+    float cull2 = point_cull(best2, slack);
+    int sp = 0;
+    int32_t ref = 0;
+    while (true) {
+        if (ref >= 0) {
+            ++visits;
+            if (W == 4) {
+                const float4 *np = reinterpret_cast<const float4 *>(sc.nodes4f + ref);
+                const float4 lx = np[0], ly = np[1], lz = np[2], hx = np[3], hy = np[4], hz = np[5];
+                const int4 ch = *reinterpret_cast<const int4 *>(np + 6);
+                int32_t rc[4] = {ch.x, ch.y, ch.z, ch.w};
+                const float blx[4] = {lx.x, lx.y, lx.z, lx.w}, bly[4] = {ly.x, ly.y, ly.z, ly.w}, blz[4] = {lz.x, lz.y, lz.z, lz.w};
+                const float bhx[4] = {hx.x, hx.y, hx.z, hx.w}, bhy[4] = {hy.x, hy.y, hy.z, hy.w}, bhz[4] = {hz.x, hz.y, hz.z, hz.w};
+                float tc[4];   // a wanted child's key is finite; INFINITY marks the others (empty slots among them)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float db2 = box_dist2(p, blx[k], bly[k], blz[k], bhx[k], bhy[k], bhz[k]);
+                    tc[k] = (db2 <= cull2 && rc[k] != kBvhEmpty) ? fminf(db2, FLT_MAX) : INFINITY;
+                }
+                const int nh = (tc[0] != INFINITY) + (tc[1] != INFINITY) + (tc[2] != INFINITY) + (tc[3] != INFINITY);
+                if (nh > 1) {
+                    cswap(tc[0], rc[0], tc[1], rc[1]);
+                    cswap(tc[2], rc[2], tc[3], rc[3]);
+                    cswap(tc[0], rc[0], tc[2], rc[2]);
+                    cswap(tc[1], rc[1], tc[3], rc[3]);
+                    cswap(tc[1], rc[1], tc[2], rc[2]);
+                } else {
+                    rc[0] = tc[0] != INFINITY ? rc[0] : tc[1] != INFINITY ? rc[1] : tc[2] != INFINITY ? rc[2] : rc[3];
+                }
+                if (nh > 3) stack.push(sp, rc[3]);   // far to near: the nearest of them ends on top
+                if (nh > 2) stack.push(sp, rc[2]);
+                if (nh > 1) stack.push(sp, rc[1]);
+                if (nh > 0) { ref = rc[0]; continue; }
+            } else {
+                const float4 *np = reinterpret_cast<const float4 *>(sc.nodes + ref);
+                const float4 q0 = np[0], q1 = np[1], q2 = np[2], q3 = np[3];
+                const float e0 = box_dist2(p, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y);
+                const float e1 = box_dist2(p, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w);
+                const int32_t c0 = __float_as_int(q3.x), c1 = __float_as_int(q3.y);
+                const bool h0 = e0 <= cull2 && c0 != kBvhEmpty, h1 = e1 <= cull2 && c1 != kBvhEmpty;
+                if (h0 && h1) {
+                    const bool first0 = e0 <= e1;
+                    stack.push(sp, first0 ? c1 : c0);
+                    ref = first0 ? c0 : c1;
+                    continue;
+                }
+                if (h0 || h1) { ref = h0 ? c0 : c1; continue; }
+            }
+        } else {
+            const uint32_t u = static_cast<uint32_t>(ref);
+            const int cnt = static_cast<int>((u >> kBvhCountShift) & kBvhCountMask);
+            const int first = static_cast<int>(u & ((1u << kBvhCountShift) - 1u));
+            bool better = false;
+            for (int k = 0; k < cnt; ++k)
+                better |= point_eval(leaf_rec(sc, first + k), static_cast<int>(sc.leaf_idx[first + k]), p, best2, bidx);
+            tests += static_cast<unsigned>(cnt);
+            if (better) cull2 = point_cull(best2, slack);
+        }
+        if (sp == 0) break;
+        ref = stack.pop(sp);
+    }
+}
+
+template <int W, int kStride, bool kCount>
+__global__ __launch_bounds__(kBvhBlock) void k_bvh_point_query(const DevScene sc, const void *__restrict__ pts, int n,
+                                                               const int32_t *__restrict__ d_count, const PointQuery q) {
+    extern __shared__ int32_t lds_stack[];
+    const LaneStack stack = lane_stack(sc, lds_stack);
+    WorkTally<kCount> wt;
+    drive_queries(live_rays(d_count, n), 0, nullptr, [&](int j, int end) {
+        const bool active = j < end;
+        V3 p = mk(0, 0, 0);
+        float best2 = INFINITY;
+        bool walk = false;
+        if (active) {
+            p = load_ray_point<kStride>(pts, j);
+            walk = load_point_bound(q.rmax, j, p, best2);
+        }
+        int bidx = -1;
+        wt.begin();
+        bvh_point_walk<W>(sc, p, walk, best2, bidx, stack, wt.tests, wt.visits);
+        wt.end();
+        if (!walk) bidx = -1;   // (the always list is tested for the idle lanes too)
+        if (active) store_point(sc.tris, j, bidx, p, q);
+    });
+    wt.flush(sc.work);
+}
+
+// The same over every triangle in index order (RT_ACCEL_BRUTE_FORCE, or no tree could be built).
+template <int kStride>
+__global__ __launch_bounds__(kBlock) void k_point_query(const TriRec *__restrict__ tris, int nt, const void *__restrict__ pts, int n,
+                                                        const int32_t *__restrict__ d_count, const PointQuery q) {
+    const int live = live_rays(d_count, n);
+    const int64_t base = static_cast<int64_t>(blockIdx.x) * kBlock;
+    if (base >= live) return;
+    const bool active = base + threadIdx.x < live;
+    const int j = active ? static_cast<int>(base + threadIdx.x) : 0;
+    V3 p = mk(0, 0, 0);
+    float best2 = INFINITY;
+    bool walk = false;
+    if (active) {
+        p = load_ray_point<kStride>(pts, j);
+        walk = load_point_bound(q.rmax, j, p, best2);
+    }
+    int bidx = -1;
+    for (int i = 0; i < nt; ++i) point_eval(tris[i], i, p, best2, bidx);
+    if (!walk) bidx = -1;
+    if (active) store_point(tris, j, bidx, p, q);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Sample generation: main.cpp:377-386 for every sub-sample of the batch's tiles.
 // ---------------------------------------------------------------------------------------------
 // (Indices are below 2^31: batches are capped at 2^30 samples and tile ids at 2^30, rt_capi.cpp.)
@@ -4562,6 +4796,29 @@ void launch_multi_rays(const DevScene &s, bool count_all, bool to_dest, const vo
         if (wide) launch_multi_mode<4, false>(s, org, dst, n, d_count, q, stream);
         else launch_multi_mode<3, false>(s, org, dst, n, d_count, q, stream);
     }
+}
+
+namespace {
+template <int kStride>
+void launch_point_mode(const DevScene &s0, const void *pts, int32_t n, const int32_t *d_count, const PointQuery &q, hipStream_t stream) {
+    if (s0.use_bvh) {   // launch_range_mode's shape
+        const int W = s0.bvh_width == 4 ? 4 : 2;
+        const DevScene s = for_width(s0, W);
+        auto k = W == 4 ? (s.work ? k_bvh_point_query<4, kStride, true> : k_bvh_point_query<4, kStride, false>)
+                        : (s.work ? k_bvh_point_query<2, kStride, true> : k_bvh_point_query<2, kStride, false>);
+        hipLaunchKernelGGL(k, dim3(grid_bvh(n, s.bvh_grid)), dim3(kBvhBlock), bvh_lds(s), stream, s, pts, n, d_count, q);
+        return;
+    }
+    hipLaunchKernelGGL((k_point_query<kStride>), dim3(grid_for(n)), dim3(kBlock), 0, stream, s0.tris, s0.nt, pts, n, d_count, q);
+}
+}  // namespace
+
+void launch_point_query(const DevScene &s, const void *pts, int32_t point_stride, int32_t n, const int32_t *d_count,
+                        const float *d_rmax, void *hit, float *point, hipStream_t stream) {
+    if (n <= 0) return;
+    const PointQuery q{d_rmax, static_cast<int4 *>(hit), point};
+    if (point_stride == 4) launch_point_mode<4>(s, pts, n, d_count, q, stream);
+    else launch_point_mode<3>(s, pts, n, d_count, q, stream);
 }
 
 void launch_gen_rays_device(const void *org, const void *dst, int32_t ray_stride, int32_t n, const DevWork &w, hipStream_t stream) {
