@@ -24,6 +24,8 @@
  *   rt_occluded_range_device  (an extension: occlusion within a range, isShadow's rule or any opaque triangle)
  *   rt_multi_hit_range_device  (an extension: the first k hits of each ray within a range, from one walk)
  *   rt_closest_point_device  (an extension: the nearest point of the mesh to each query point)
+ *   rt_nearest_triangles_device / rt_within_radius_device  (extensions: the k nearest triangles of each query
+ *                         point, and whether it has one inside its radius)
  *   rt_debug_trace       debug key 'd' (shoot + trace)     raytracing.cpp:493-510
  *                         (batched; also trace(o,d,lvl) at lvl 0, raytracing.h:30)
  *   rt_render_tile        the 'r'-key frame loop            main.cpp:340-411 (loop :355-395,
@@ -415,6 +417,34 @@ int rt_closest_point_device(rt_scene *scene, const void *d_points, int32_t point
  * copy in, the same launch, copy out, synchronise. The same bits. */
 int rt_closest_point(rt_scene *scene, const float *points, int32_t n, const float *rmax,
                      rt_hit *hit_out, float *point_out);
+/* The k nearest triangles of each query point, from one walk. The definition adds no arithmetic: candidate, dist2,
+ * s, t, c and bound_i are exactly those of rt_closest_point_device above (a NaN or infinite point component and a
+ * NaN, zero or negative radius are empty searches; with d_rmax NULL the bound is +inf). Let m be the number of
+ * candidates of point i with dist2 < bound_i.
+ * d_hits_out (n x k rt_hit, point-major, 16-byte aligned): rows [i k, i k + min(m, k)) are those candidates in
+ * ascending lexicographic (dist2, triangle index) order, each {triangle, sqrtf(dist2), s, t} with the bits
+ * rt_closest_point_device computes for that triangle and point; the point's other rows are the miss record
+ * {-1, +inf, 0, 0}. Triangles at an equal dist2 (a shared vertex or edge) all appear, lowest index first.
+ * d_points_out (n x k x 3 packed floats, may be NULL): c of each row's record, or (0,0,0) on a miss row.
+ * d_nfound_out (n x int32, 4-byte aligned; may be NULL unless RT_NEAR_COUNT_ALL): min(m, k), or with
+ * RT_NEAR_COUNT_ALL m itself (so a caller sees that k truncated the list); the hit rows are the same bytes
+ * whether or not the flag is set. k is in [1, RT_MULTI_HIT_MAX]; with k = 1 and no flag, row i and its point are
+ * rt_closest_point_device's bytes. The result does not depend on the acceleration structure.
+ * d_points, point_stride, d_count, d_rmax, stream, the ordering against updates, rebuilds, rt_scene_set_mesh and
+ * rt_scene_destroy, and rows at or past the live count (neither read nor written) as rt_closest_point_device.
+ * Errors in that entry's order: RT_E_NODEV on a host-only scene before anything else; RT_E_ARG for a NULL scene,
+ * n < 0, a bad stride, NULL or misaligned arrays, k out of range, any flag but RT_NEAR_COUNT_ALL, that flag with a
+ * NULL d_nfound_out, n * k above INT32_MAX; n == 0 returns RT_OK with nothing enqueued. */
+#define RT_NEAR_COUNT_ALL (1u << 3)   /* d_nfound_out = every candidate inside the bound, not min(m, k) */
+int rt_nearest_triangles_device(rt_scene *scene, const void *d_points, int32_t point_stride, int32_t n,
+                                const void *d_count, const void *d_rmax, uint32_t flags, int32_t k,
+                                void *d_hits_out, void *d_nfound_out, void *d_points_out, void *stream);
+/* Whether anything lies within the radius: d_within_out[i] (n x uint8) is 1 when m > 0 and 0 otherwise, that is,
+ * 1 exactly when rt_closest_point_device returns a triangle for that point; the walk leaves a point at its first
+ * candidate below the bound. flags must be 0 (RT_E_ARG otherwise). Everything else as the entry above. */
+int rt_within_radius_device(rt_scene *scene, const void *d_points, int32_t point_stride, int32_t n,
+                            const void *d_count, const void *d_rmax, uint32_t flags,
+                            void *d_within_out, void *stream);
 /* performRayTracing (raytracing.cpp:410-416) for rays in device memory: d_rgb_out[3*i..] (3n packed floats),
  * bit for bit rt_trace_rays' rgb_out. counts as in rt_trace_rays; non-NULL synchronises the stream. Uses
  * render pipeline 0's workspace (ordered against the frames that use it): returns after enqueueing when

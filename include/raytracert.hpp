@@ -221,6 +221,18 @@ class RayTracer {
                               uint32_t flags, void *d_hit_out, void *d_point_out, void *stream) {
         check(rt_closest_point_device(scene_, d_points, point_stride, n, d_count, d_rmax, flags, d_hit_out, d_point_out, stream));
     }
+    // the k nearest triangles of each query point (rt_nearest_triangles_device: d_hits_out n x k rt_hit, d_nfound_out
+    // n int32 or null, d_points_out n x k x 3 floats or null; flags: RT_NEAR_COUNT_ALL)
+    void nearest_triangles_device(const void *d_points, int32_t point_stride, int32_t n, const void *d_count, const void *d_rmax,
+                                  uint32_t flags, int32_t k, void *d_hits_out, void *d_nfound_out, void *d_points_out, void *stream) {
+        check(rt_nearest_triangles_device(scene_, d_points, point_stride, n, d_count, d_rmax, flags, k, d_hits_out, d_nfound_out,
+                                          d_points_out, stream));
+    }
+    // whether each query point has a triangle inside its radius (rt_within_radius_device: d_within_out n x uint8; flags 0)
+    void within_radius_device(const void *d_points, int32_t point_stride, int32_t n, const void *d_count, const void *d_rmax,
+                              uint32_t flags, void *d_within_out, void *stream) {
+        check(rt_within_radius_device(scene_, d_points, point_stride, n, d_count, d_rmax, flags, d_within_out, stream));
+    }
     void perform_ray_tracing_device(const void *d_origins, const void *d_dests, int32_t ray_stride, int32_t n, void *d_rgb_out,
                                     void *stream, uint64_t counts[3] = nullptr) {
         rt_params p = params();

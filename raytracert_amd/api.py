@@ -520,6 +520,57 @@ class Scene:
         res = (rec[:n, 0], f[:, 1], f[:, 2:4])
         return res + (pts[:n],) if want_points else res
 
+    def nearest_triangles_device(self, points, k: int, rmax=None, count_all: bool = False, count=None, out=None,
+                                 want_points: bool = False, stream=None):
+        """rt_nearest_triangles_device: per query point, the k (1.._capi.MULTI_HIT_MAX) nearest candidate triangles
+        inside the point's radius, in ascending (squared distance, index) order, from one walk. points, rmax, count
+        and stream as closest_point_device. Returns (triangle[n, k] int32, distance[n, k] float32, st[n, k, 2] float32,
+        nfound[n] int32) and with want_points also point[n, k, 3]: the first three are views of one (n, k, 4) int32
+        record tensor whose rows past a point's triangles are the miss record (-1, +inf, 0, 0), with the point
+        (0, 0, 0); nfound is the number of rows that hold a triangle, or with count_all the number of candidates
+        inside the radius (which may exceed k). Triangles at one distance all appear, lowest index first; k = 1 is
+        closest_point_device's record. out: a (records, nfound) pair to write into, (>= n, k, 4) int32 and (>= n,)
+        int32, or with want_points a (records, nfound, points) triple with (>= n, k, 3) float32."""
+        import torch
+        name = "nearest_triangles_device"
+        if not isinstance(k, int) or isinstance(k, bool) or k < 1 or k > _capi.MULTI_HIT_MAX:
+            raise ValueError(f"{name}: k must be an int in [1, {_capi.MULTI_HIT_MAX}], not {k!r}")
+        n, stride = self._device_rays(name, "closest_point", points, points, ("points", "points"))
+        cnt = self._device_count(name, count)
+        rad = self._device_bound(name, "rmax", rmax, n)
+        parts = 3 if want_points else 2
+        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != parts):
+            raise ValueError(f"{name}: out must be a (records, nfound{', points' if want_points else ''}) tuple")
+        rec = self._device_out(name, None if out is None else out[0], n, torch.int32, (k, 4), 0, False)
+        if out is None and count is not None:          # entries a device count leaves unwritten: the miss record
+            rec[..., 0], rec[..., 1], rec[..., 2:] = -1, 0x7F800000, 0      # (device fills: no host copy)
+        if rec.data_ptr() % _capi.HIT_BYTES:
+            raise ValueError(f"{name}: the record tensor must be 16-byte aligned")
+        nf = self._device_out(name, None if out is None else out[1], n, torch.int32, (), 0, count is not None)
+        pts = self._device_out(name, None if out is None else out[2], n, torch.float32, (k, 3), 0.0, count is not None) if want_points else None
+        check(lib().rt_nearest_triangles_device(self._h, C.c_void_p(points.data_ptr()), stride, n, cnt, rad,
+                                                _capi.NEAR_COUNT_ALL if count_all else 0, k, C.c_void_p(rec.data_ptr()),
+                                                C.c_void_p(nf.data_ptr()), None if pts is None else C.c_void_p(pts.data_ptr()),
+                                                self._stream_ptr(stream)))
+        f = rec[:n].view(torch.float32)
+        res = (rec[:n, :, 0], f[:, :, 1], f[:, :, 2:4], nf[:n])
+        return res + (pts[:n],) if want_points else res
+
+    def within_radius_device(self, points, rmax=None, count=None, out=None, stream=None):
+        """rt_within_radius_device: within[n] uint8, 1 where the point has a candidate triangle nearer than its radius
+        (where closest_point_device with the same rmax returns a triangle), else 0; the walk leaves a point at the
+        first such triangle. points, rmax, count and stream as closest_point_device; out: a (>= n,) uint8 tensor to
+        write into."""
+        import torch
+        name = "within_radius_device"
+        n, stride = self._device_rays(name, "closest_point", points, points, ("points", "points"))
+        cnt = self._device_count(name, count)
+        rad = self._device_bound(name, "rmax", rmax, n)
+        within = self._device_out(name, out, n, torch.uint8, (), 0, count is not None)
+        check(lib().rt_within_radius_device(self._h, C.c_void_p(points.data_ptr()), stride, n, cnt, rad, 0,
+                                            C.c_void_p(within.data_ptr()), self._stream_ptr(stream)))
+        return within[:n]
+
     def closest_point(self, points, rmax=None):
         """rt_closest_point for numpy arrays: returns (triangle[n] int32, distance[n] float32, st[n, 2] float32,
         point[n, 3] float32), closest_point_device's bits. rmax: optional n search radii."""

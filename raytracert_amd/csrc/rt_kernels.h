@@ -231,6 +231,17 @@ void launch_multi_rays(const DevScene &s, bool count_all, bool to_dest, const vo
 // give the same bytes.
 void launch_point_query(const DevScene &s, const void *pts, int32_t point_stride, int32_t n, const int32_t *d_count,
                         const float *d_rmax, void *hit, float *point, hipStream_t stream);
+// Nearest-triangle device query (rt_nearest_triangles_device): per point the k candidates below its bound with
+// the smallest (dist2, index), in that order, as hits[n][k] records (rows past the list: the miss record),
+// points[n][k][3] when not null, and nfound[n] when not null: the rows that hold a triangle, or with count_all
+// every candidate below the bound. The rest as launch_point_query. The tree walk (k_bvh_near_query) and the
+// loop over every triangle (k_point_list_query) give the same bytes.
+void launch_near_query(const DevScene &s, bool count_all, const void *pts, int32_t point_stride, int32_t n, const int32_t *d_count,
+                       const float *d_rmax, int32_t k, void *hits, int32_t *nfound, float *points, hipStream_t stream);
+// rt_within_radius_device: within[n] = 1 when the point has a candidate below its bound, else 0 (the any
+// mode of the same walk; k_point_any_query over every triangle).
+void launch_within_query(const DevScene &s, const void *pts, int32_t point_stride, int32_t n, const int32_t *d_count,
+                         const float *d_rmax, uint8_t *within, hipStream_t stream);
 // launch_gen_rays from the caller's device arrays in either layout (rt_trace_rays_device)
 void launch_gen_rays_device(const void *org, const void *dst, int32_t ray_stride, int32_t n, const DevWork &w,
                             hipStream_t stream);

@@ -2012,6 +2012,258 @@ __global__ __launch_bounds__(kBlock) void k_point_query(const TriRec *__restrict
 }
 
 // ---------------------------------------------------------------------------------------------
+// Nearest-triangle queries (rt_nearest_triangles_device, rt_within_radius_device): per query point the k
+// candidates with the smallest (dist2, index) among those with dist2 below the point's bound, as k rt_hit rows
+// in that order, or (kNearAny) only whether there is one. Candidate, dist2, s, t, c and the bound are the
+// closest-point query's (closest_on_triangle, point_candidate, load_point_bound); nothing is computed that
+// that query does not compute. A key is hit_key(dist2, index): dist2 is a sum of squares, never negative, so
+// its bits order as the floats do, and a NaN dist2 passes neither compare of near_eval.
+//
+// The list is MultiList's ([k][block lanes] 64-bit keys in dynamic LDS behind the traversal stack, as
+// k_bvh_multi_rays lays it out), driven as that struct states: the walk's own best2 / bidx are the admission
+// bound, (bound, -1) while the list holds fewer than k keys, so point_eval's test admits exactly dist2 < bound,
+// then the k-th key, so it admits exactly the keys below that one. kNearListAll (RT_NEAR_COUNT_ALL): best2
+// stays the bound, every candidate below it is counted once (a walk meets a triangle at most once: it is on
+// the always list or in exactly one leaf), and the list keeps its k-th key as a bound of its own.
+//
+// Exactness: the argument above bvh_point_walk (DESIGN.md §7 "Closest-point queries") with kd in place of
+// best2, kd = best2 here: the bound while the list is not full, the k-th key's dist2 once it is. A child is
+// skipped only when its box distance exceeds point_cull(kd, slack), which puts every candidate below it at a
+// dist2 strictly above kd. With a list that is not full such a candidate is outside the bound; with a full one
+// it is strictly beyond the k-th key, so it can neither be among the k smallest nor tie with the k-th. kd only
+// falls, so a subtree skipped once stays skippable, every insertion keeps the k smallest keys met so far, and
+// the result is the k smallest keys of the bounded set whatever the tree and the visiting order. cull2 is
+// recomputed only when kd changes: a node visit costs no sqrtf. kNearListAll never lowers best2, so it walks
+// the whole ball; kNearAny keeps no list, never lowers it either, and a lane leaves at its first candidate
+// below the bound (nearest child first, so usually soon).
+// The node step is bvh_point_walk's, repeated here so that the closest-point kernels compile as they did.
+// After the walk each kept triangle's record is recomputed from the scene's record (as store_point does) and
+// stored as one 16-byte row; rows past the list are the miss record. An empty search (load_point_bound) takes
+// no part in the walk: k miss rows, a count of 0, a verdict of 0.
+// ---------------------------------------------------------------------------------------------
+enum : int { kNearList = 0, kNearListAll = 1, kNearAny = 2 };
+struct NearQuery {
+    const float *rmax;          // per point, or null
+    int32_t k;
+    int4 *hit;                  // [n][k] records (list modes)
+    int32_t *nfound;            // [n], or null
+    float *point;               // [n][k][3], or null
+    uint8_t *within;            // [n] (kNearAny)
+};
+
+// One candidate against the admission bound (best2, bidx). true when best2, the bound the walk culls by,
+// changed; kNearAny: found is set instead and nothing else changes.
+template <int kMode>
+__device__ __forceinline__ bool near_eval(const TriRec &T, int idx, V3 p, float &best2, int &bidx, MultiList &ml, bool &found) {
+    if (!point_candidate(T)) return false;
+    float s, t;
+    V3 c;
+    const float d2 = closest_on_triangle(T, p, s, t, c);
+    if (!(d2 < best2 || (d2 == best2 && bidx >= 0 && idx < bidx))) return false;
+    if (kMode == kNearAny) {
+        found = true;
+        return false;
+    }
+    const float before = best2;
+    ml.admit<kMode == kNearListAll>(d2, idx, best2, bidx);
+    return best2 != before;
+}
+
+template <int W, int kMode>
+__device__ __forceinline__ void bvh_point_walk_list(const DevScene &sc, V3 p, bool walk, float &best2, int &bidx, MultiList &ml,
+                                                    bool &found, const LaneStack &stack, unsigned &tests, unsigned &visits) {
+    // the always list: wave-uniform records, every lane
+    for (int i = 0; i < sc.n_always; ++i) {
+        if (kMode == kNearAny && found) continue;
+        near_eval<kMode>(sc.always_recs[i], static_cast<int>(sc.always[i]), p, best2, bidx, ml, found);
+    }
+    tests += static_cast<unsigned>(max(sc.n_always, 0));
+    if (!walk || found) return;
+    const float slack = 32.0f * 5.9604645e-08f * ((fabsf(p.x) + fabsf(p.y) + fabsf(p.z)) + sc.scene_m1);
+    float cull2 = point_cull(best2, slack);
+    int sp = 0;
+    int32_t ref = 0;
+    while (true) {
+        if (ref >= 0) {
+            ++visits;
+            if (W == 4) {
+                const float4 *np = reinterpret_cast<const float4 *>(sc.nodes4f + ref);
+                const float4 lx = np[0], ly = np[1], lz = np[2], hx = np[3], hy = np[4], hz = np[5];
+                const int4 ch = *reinterpret_cast<const int4 *>(np + 6);
+                int32_t rc[4] = {ch.x, ch.y, ch.z, ch.w};
+                const float blx[4] = {lx.x, lx.y, lx.z, lx.w}, bly[4] = {ly.x, ly.y, ly.z, ly.w}, blz[4] = {lz.x, lz.y, lz.z, lz.w};
+                const float bhx[4] = {hx.x, hx.y, hx.z, hx.w}, bhy[4] = {hy.x, hy.y, hy.z, hy.w}, bhz[4] = {hz.x, hz.y, hz.z, hz.w};
+                float tc[4];   // a wanted child's key is finite; INFINITY marks the others (empty slots among them)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float db2 = box_dist2(p, blx[k], bly[k], blz[k], bhx[k], bhy[k], bhz[k]);
+                    tc[k] = (db2 <= cull2 && rc[k] != kBvhEmpty) ? fminf(db2, FLT_MAX) : INFINITY;
+                }
+                const int nh = (tc[0] != INFINITY) + (tc[1] != INFINITY) + (tc[2] != INFINITY) + (tc[3] != INFINITY);
+                if (nh > 1) {
+                    cswap(tc[0], rc[0], tc[1], rc[1]);
+                    cswap(tc[2], rc[2], tc[3], rc[3]);
+                    cswap(tc[0], rc[0], tc[2], rc[2]);
+                    cswap(tc[1], rc[1], tc[3], rc[3]);
+                    cswap(tc[1], rc[1], tc[2], rc[2]);
+                } else {
+                    rc[0] = tc[0] != INFINITY ? rc[0] : tc[1] != INFINITY ? rc[1] : tc[2] != INFINITY ? rc[2] : rc[3];
+                }
+                if (nh > 3) stack.push(sp, rc[3]);   // far to near: the nearest of them ends on top; each wanted
+                if (nh > 2) stack.push(sp, rc[2]);   // child is pushed or taken, never both, so no subtree is
+                if (nh > 1) stack.push(sp, rc[1]);   // walked twice (a count would notice)
+                if (nh > 0) { ref = rc[0]; continue; }
+            } else {
+                const float4 *np = reinterpret_cast<const float4 *>(sc.nodes + ref);
+                const float4 q0 = np[0], q1 = np[1], q2 = np[2], q3 = np[3];
+                const float e0 = box_dist2(p, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y);
+                const float e1 = box_dist2(p, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w);
+                const int32_t c0 = __float_as_int(q3.x), c1 = __float_as_int(q3.y);
+                const bool h0 = e0 <= cull2 && c0 != kBvhEmpty, h1 = e1 <= cull2 && c1 != kBvhEmpty;
+                if (h0 && h1) {
+                    const bool first0 = e0 <= e1;
+                    stack.push(sp, first0 ? c1 : c0);
+                    ref = first0 ? c0 : c1;
+                    continue;
+                }
+                if (h0 || h1) { ref = h0 ? c0 : c1; continue; }
+            }
+        } else {
+            const uint32_t u = static_cast<uint32_t>(ref);
+            const int cnt = static_cast<int>((u >> kBvhCountShift) & kBvhCountMask);
+            const int first = static_cast<int>(u & ((1u << kBvhCountShift) - 1u));
+            if (kMode == kNearAny) {
+                for (int k = 0; k < cnt && !found; ++k) {
+                    near_eval<kMode>(leaf_rec(sc, first + k), static_cast<int>(sc.leaf_idx[first + k]), p, best2, bidx, ml, found);
+                    ++tests;
+                }
+                if (found) return;
+            } else {
+                bool lower = false;
+                for (int k = 0; k < cnt; ++k)
+                    lower |= near_eval<kMode>(leaf_rec(sc, first + k), static_cast<int>(sc.leaf_idx[first + k]), p, best2, bidx, ml, found);
+                tests += static_cast<unsigned>(cnt);
+                if (lower) cull2 = point_cull(best2, slack);
+            }
+        }
+        if (sp == 0) break;
+        ref = stack.pop(sp);
+    }
+}
+
+// The rows of one point: the list's keys in order, each triangle's record recomputed, then miss rows.
+template <int kMode>
+__device__ __forceinline__ void store_near(const TriRec *__restrict__ tris, const MultiList &ml, int j, V3 p, const NearQuery &q) {
+    const size_t row0 = static_cast<size_t>(j) * static_cast<size_t>(ml.k);
+    for (int i = 0; i < ml.k; ++i) {
+        int4 rec = make_int4(-1, as_int(INFINITY), 0, 0);
+        V3 c = mk(0, 0, 0);
+        if (i < ml.cnt) {
+            const int idx = static_cast<int>(static_cast<uint32_t>(ml.keys[i * ml.width]));
+            float s, t;
+            const float d2 = closest_on_triangle(tris[idx], p, s, t, c);
+            rec = make_int4(idx, as_int(sqrtf(d2)), as_int(s), as_int(t));
+        }
+        q.hit[row0 + i] = rec;                                                     // one 16-byte store
+        if (q.point) reinterpret_cast<V3 *>(q.point)[row0 + i] = c;
+    }
+    if (q.nfound) q.nfound[j] = kMode == kNearListAll ? ml.total : ml.cnt;
+}
+
+template <int W, int kStride, bool kCount, int kMode>
+__global__ __launch_bounds__(kBvhBlock) void k_bvh_near_query(const DevScene sc, const void *__restrict__ pts, int n,
+                                                              const int32_t *__restrict__ d_count, const NearQuery q) {
+    extern __shared__ int32_t lds_stack[];
+    const LaneStack stack = lane_stack(sc, lds_stack);
+    unsigned long long *const lists = reinterpret_cast<unsigned long long *>(lds_stack + max(sc.lds_stack, 1) * kBvhBlock);
+    WorkTally<kCount> wt;
+    drive_queries(live_rays(d_count, n), 0, nullptr, [&](int j, int end) {
+        const bool active = j < end;
+        V3 p = mk(0, 0, 0);
+        float best2 = INFINITY;
+        bool walk = false;
+        if (active) {
+            p = load_ray_point<kStride>(pts, j);
+            walk = load_point_bound(q.rmax, j, p, best2);
+        }
+        MultiList ml;
+        ml.keys = lists + threadIdx.x;   // (kNearAny: never touched, and the launch has no LDS for it)
+        ml.width = kBvhBlock;
+        ml.k = kMode == kNearAny ? 0 : q.k;
+        ml.kd = best2;
+        int bidx = -1;
+        // a lane that does not search evaluates the always list with the others, below a bound that nothing
+        // passes (r * r of a negative radius would admit)
+        if (!walk) { best2 = -1.0f; ml.kd = -1.0f; }
+        bool found = false;
+        wt.begin();
+        bvh_point_walk_list<W, kMode>(sc, p, walk, best2, bidx, ml, found, stack, wt.tests, wt.visits);
+        wt.end();
+        if (!active) return;
+        if (kMode == kNearAny) q.within[j] = walk && found ? 1 : 0;
+        else store_near<kMode>(sc.tris, ml, j, p, q);
+    });
+    wt.flush(sc.work);
+}
+
+// The same over every triangle in index order (RT_ACCEL_BRUTE_FORCE, or no tree could be built).
+template <int kStride, bool kCountAll>
+__global__ __launch_bounds__(kBlock) void k_point_list_query(const TriRec *__restrict__ tris, int nt, const void *__restrict__ pts, int n,
+                                                             const int32_t *__restrict__ d_count, const NearQuery q) {
+    extern __shared__ int32_t lds_stack[];   // the lists alone
+    const int live = live_rays(d_count, n);
+    const int64_t base = static_cast<int64_t>(blockIdx.x) * kBlock;
+    if (base >= live) return;
+    const bool active = base + threadIdx.x < live;
+    const int j = active ? static_cast<int>(base + threadIdx.x) : 0;
+    V3 p = mk(0, 0, 0);
+    float best2 = INFINITY;
+    bool walk = false;
+    if (active) {
+        p = load_ray_point<kStride>(pts, j);
+        walk = load_point_bound(q.rmax, j, p, best2);
+    }
+    if (!walk) best2 = -1.0f;   // (nothing is below it)
+    MultiList ml;
+    ml.keys = reinterpret_cast<unsigned long long *>(lds_stack) + threadIdx.x;
+    ml.width = kBlock;
+    ml.k = q.k;
+    ml.kd = best2;
+    int bidx = -1;
+    bool found = false;
+    for (int i = 0; i < nt; ++i) near_eval<kCountAll ? kNearListAll : kNearList>(tris[i], i, p, best2, bidx, ml, found);
+    if (active) store_near<kCountAll ? kNearListAll : kNearList>(tris, ml, j, p, q);
+}
+
+template <int kStride>
+__global__ __launch_bounds__(kBlock) void k_point_any_query(const TriRec *__restrict__ tris, int nt, const void *__restrict__ pts, int n,
+                                                            const int32_t *__restrict__ d_count, const NearQuery q) {
+    const int live = live_rays(d_count, n);
+    const int64_t base = static_cast<int64_t>(blockIdx.x) * kBlock;
+    if (base >= live) return;
+    const bool active = base + threadIdx.x < live;
+    const int j = active ? static_cast<int>(base + threadIdx.x) : 0;
+    V3 p = mk(0, 0, 0);
+    float best2 = INFINITY;
+    bool walk = false;
+    if (active) {
+        p = load_ray_point<kStride>(pts, j);
+        walk = load_point_bound(q.rmax, j, p, best2);
+    }
+    MultiList ml;               // (unused: kNearAny keeps no list)
+    ml.keys = nullptr;
+    ml.width = 0;
+    ml.k = 0;
+    int bidx = -1;
+    bool found = !walk;         // a lane that does not search has nothing to look for
+    for (int i = 0; i < nt; ++i) {
+        if ((i & 15) == 0 && __all(found)) break;
+        if (!found) near_eval<kNearAny>(tris[i], i, p, best2, bidx, ml, found);
+    }
+    if (active) q.within[j] = walk && found ? 1 : 0;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Sample generation: main.cpp:377-386 for every sub-sample of the batch's tiles.
 // ---------------------------------------------------------------------------------------------
 // (Indices are below 2^31: batches are capped at 2^30 samples and tile ids at 2^30, rt_capi.cpp.)
@@ -4819,6 +5071,48 @@ void launch_point_query(const DevScene &s, const void *pts, int32_t point_stride
     const PointQuery q{d_rmax, static_cast<int4 *>(hit), point};
     if (point_stride == 4) launch_point_mode<4>(s, pts, n, d_count, q, stream);
     else launch_point_mode<3>(s, pts, n, d_count, q, stream);
+}
+
+namespace {
+template <int kStride, int kMode>
+void launch_near_mode(const DevScene &s0, const void *pts, int32_t n, const int32_t *d_count, const NearQuery &q, hipStream_t stream) {
+    constexpr bool kList = kMode != kNearAny;
+    if (s0.use_bvh) {   // launch_multi_mode's shape; the lists' LDS follows the stack's
+        const int W = s0.bvh_width == 4 ? 4 : 2;
+        const DevScene s = for_width(s0, W);
+        auto k = W == 4 ? (s.work ? k_bvh_near_query<4, kStride, true, kMode> : k_bvh_near_query<4, kStride, false, kMode>)
+                        : (s.work ? k_bvh_near_query<2, kStride, true, kMode> : k_bvh_near_query<2, kStride, false, kMode>);
+        hipLaunchKernelGGL(k, dim3(grid_bvh(n, s.bvh_grid)), dim3(kBvhBlock), bvh_lds(s) + (kList ? multi_lds(q.k, kBvhBlock) : 0), stream,
+                           s, pts, n, d_count, q);
+        return;
+    }
+    if (kList)
+        hipLaunchKernelGGL((k_point_list_query<kStride, kMode == kNearListAll>), dim3(grid_for(n)), dim3(kBlock), multi_lds(q.k, kBlock),
+                           stream, s0.tris, s0.nt, pts, n, d_count, q);
+    else
+        hipLaunchKernelGGL((k_point_any_query<kStride>), dim3(grid_for(n)), dim3(kBlock), 0, stream, s0.tris, s0.nt, pts, n, d_count, q);
+}
+template <int kMode>
+void launch_near_stride(const DevScene &s, const void *pts, int32_t point_stride, int32_t n, const int32_t *d_count, const NearQuery &q,
+                        hipStream_t stream) {
+    if (point_stride == 4) launch_near_mode<4, kMode>(s, pts, n, d_count, q, stream);
+    else launch_near_mode<3, kMode>(s, pts, n, d_count, q, stream);
+}
+}  // namespace
+
+void launch_near_query(const DevScene &s, bool count_all, const void *pts, int32_t point_stride, int32_t n, const int32_t *d_count,
+                       const float *d_rmax, int32_t k, void *hits, int32_t *nfound, float *points, hipStream_t stream) {
+    if (n <= 0) return;
+    const NearQuery q{d_rmax, k, static_cast<int4 *>(hits), nfound, points, nullptr};
+    if (count_all) launch_near_stride<kNearListAll>(s, pts, point_stride, n, d_count, q, stream);
+    else launch_near_stride<kNearList>(s, pts, point_stride, n, d_count, q, stream);
+}
+
+void launch_within_query(const DevScene &s, const void *pts, int32_t point_stride, int32_t n, const int32_t *d_count,
+                         const float *d_rmax, uint8_t *within, hipStream_t stream) {
+    if (n <= 0) return;
+    const NearQuery q{d_rmax, 0, nullptr, nullptr, nullptr, within};
+    launch_near_stride<kNearAny>(s, pts, point_stride, n, d_count, q, stream);
 }
 
 void launch_gen_rays_device(const void *org, const void *dst, int32_t ray_stride, int32_t n, const DevWork &w, hipStream_t stream) {
