@@ -26,6 +26,8 @@
  *   rt_closest_point_device  (an extension: the nearest point of the mesh to each query point)
  *   rt_nearest_triangles_device / rt_within_radius_device  (extensions: the k nearest triangles of each query
  *                         point, and whether it has one inside its radius)
+ *   rt_point_inside_device / rt_signed_distance_device  (extensions: whether each query point is inside the
+ *                         mesh, by crossing parity along an axis, and the closest-point record with that sign)
  *   rt_debug_trace       debug key 'd' (shoot + trace)     raytracing.cpp:493-510
  *                         (batched; also trace(o,d,lvl) at lvl 0, raytracing.h:30)
  *   rt_render_tile        the 'r'-key frame loop            main.cpp:340-411 (loop :355-395,
@@ -445,6 +447,58 @@ int rt_nearest_triangles_device(rt_scene *scene, const void *d_points, int32_t p
 int rt_within_radius_device(rt_scene *scene, const void *d_points, int32_t point_stride, int32_t n,
                             const void *d_count, const void *d_rmax, uint32_t flags,
                             void *d_within_out, void *stream);
+/* Whether each query point is inside the mesh: the parity of the number of surface crossings of the half line
+ * from the point along a coordinate axis. It means something on a closed (watertight) mesh only; on an open mesh
+ * the count is still the defined, deterministic number below, and its parity says nothing.
+ * d_points, point_stride, d_count, stream, the ordering against updates, rebuilds, rt_scene_set_mesh and
+ * rt_scene_destroy, and rows at or past the live count (neither read nor written) as rt_closest_point_device.
+ * axis: RT_AXIS_POS_X .. RT_AXIS_NEG_Z (0..5: +x, -x, +y, -y, +z, -z). flags must be 0.
+ * d_inside_out (n x uint8): crossings_i & 1. d_crossings_out (n x int32, 4-byte aligned, may be NULL): crossings_i.
+ *
+ * The definition. The candidates are rt_closest_point_device's: every triangle whose record normal is not
+ * (0,0,0), classes 0 and 1 of rt_bvh_acceptance_box; class 2 never counts. V0, V1, V2 are the scene's current
+ * vertex array entries xyz[tri_v[3 i + j]] (not T0 + u: a shared vertex has the same bits in every triangle that
+ * uses it). With k = axis >> 1, sg = +1 for an even axis and -1 for an odd one, (a, b) = ((k + 1) % 3, (k + 2) % 3):
+ * a point with a NaN or infinite component has crossings 0. Otherwise, no contraction anywhere, per candidate:
+ *   d_j = V_j - p per component, one binary32 subtraction each                       (j = 0, 1, 2)
+ *   X_j = (double)d_j[a]     Y_j = (double)d_j[b]     Z_j = sg * (double)d_j[k]
+ *   for the edges (i0, i1) = (1, 2), (2, 0), (0, 1), giving E_0, E_1, E_2 (E_j is the edge opposite vertex j):
+ *     E = X_i0 * Y_i1 - Y_i0 * X_i1 in binary64 (both products are exact: 24-bit factors; E has the exact sign)
+ *     the edge is crossed when (Y_i0 <= 0 && Y_i1 > 0 && E > 0) || (Y_i1 <= 0 && Y_i0 > 0 && E < 0)
+ *   the triangle covers the point when an odd number of its three edges is crossed
+ *   det = (E_0 + E_1) + E_2      num = (E_0 * Z_0 + E_1 * Z_1) + E_2 * Z_2      in binary64
+ *   the triangle is above when (det > 0 && num > 0) || (det < 0 && num < 0)
+ * crossings_i = the number of candidates that both cover point i and are above it; inside_i = crossings_i & 1.
+ * Consequences: the cover test is an exact even-odd test on the projected mesh whose vertices are the d_j, so two
+ * triangles that share an edge never both claim, or both drop, a point under that edge; a point exactly under an
+ * edge (E = 0) is claimed through that edge by neither; a triangle edge-on to the axis never counts. The above test
+ * rounds (E * Z), so a point within rounding of the surface lands on either side: the sign is exact away from the
+ * surface and arbitrary but deterministic on it. Six directions let a caller vote. Coordinates are assumed small
+ * enough that V_j - p does not overflow binary32. The result does not depend on the acceleration structure: the
+ * tree walk returns the count of the loop over every triangle, on any builder, either tree width, after any refit.
+ * Errors in rt_closest_point_device's order: RT_E_NODEV on a host-only scene before anything else; RT_E_ARG for a
+ * NULL scene, n < 0, a bad stride, NULL or misaligned arrays, a non-zero flag, an axis outside 0..5; n == 0 returns
+ * RT_OK with nothing enqueued. */
+#define RT_AXIS_POS_X 0
+#define RT_AXIS_NEG_X 1
+#define RT_AXIS_POS_Y 2
+#define RT_AXIS_NEG_Y 3
+#define RT_AXIS_POS_Z 4
+#define RT_AXIS_NEG_Z 5
+int rt_point_inside_device(rt_scene *scene, const void *d_points, int32_t point_stride, int32_t n,
+                           const void *d_count, int32_t axis, uint32_t flags,
+                           void *d_inside_out /* n x uint8 */, void *d_crossings_out /* n x int32, may be NULL */,
+                           void *stream);
+/* The signed distance: d_hit_out and d_point_out are rt_closest_point_device's bytes for the same points and
+ * d_rmax, with the sign bit of `distance` set when inside_i (above, along `axis`) is 1. A miss outside stays
+ * {-1, +inf, 0, 0}; a miss inside is {-1, -inf, 0, 0}, so a narrow-band field keeps its sign beyond the band; s, t
+ * and the closest point are unchanged; a point with a NaN or infinite component is a positive miss.
+ * d_inside_out (n x uint8, may be NULL): inside_i. It is the closest-point launch followed by the inside launch on
+ * the same stream. Arguments and errors as rt_closest_point_device, then the axis. */
+int rt_signed_distance_device(rt_scene *scene, const void *d_points, int32_t point_stride, int32_t n,
+                              const void *d_count, const void *d_rmax, int32_t axis, uint32_t flags,
+                              void *d_hit_out, void *d_point_out /* may be NULL */,
+                              void *d_inside_out /* may be NULL */, void *stream);
 /* performRayTracing (raytracing.cpp:410-416) for rays in device memory: d_rgb_out[3*i..] (3n packed floats),
  * bit for bit rt_trace_rays' rgb_out. counts as in rt_trace_rays; non-NULL synchronises the stream. Uses
  * render pipeline 0's workspace (ordered against the frames that use it): returns after enqueueing when

@@ -233,6 +233,19 @@ class RayTracer {
                               uint32_t flags, void *d_within_out, void *stream) {
         check(rt_within_radius_device(scene_, d_points, point_stride, n, d_count, d_rmax, flags, d_within_out, stream));
     }
+    // whether each query point is inside the mesh, by crossing parity along an axis (rt_point_inside_device: axis
+    // RT_AXIS_POS_X .. RT_AXIS_NEG_Z, d_inside_out n x uint8, d_crossings_out n int32 or null; flags 0)
+    void point_inside_device(const void *d_points, int32_t point_stride, int32_t n, const void *d_count, int32_t axis, uint32_t flags,
+                             void *d_inside_out, void *d_crossings_out, void *stream) {
+        check(rt_point_inside_device(scene_, d_points, point_stride, n, d_count, axis, flags, d_inside_out, d_crossings_out, stream));
+    }
+    // closest_point_device with the distance negative inside the mesh (rt_signed_distance_device: d_inside_out n x uint8
+    // or null; flags 0)
+    void signed_distance_device(const void *d_points, int32_t point_stride, int32_t n, const void *d_count, const void *d_rmax,
+                                int32_t axis, uint32_t flags, void *d_hit_out, void *d_point_out, void *d_inside_out, void *stream) {
+        check(rt_signed_distance_device(scene_, d_points, point_stride, n, d_count, d_rmax, axis, flags, d_hit_out, d_point_out,
+                                        d_inside_out, stream));
+    }
     void perform_ray_tracing_device(const void *d_origins, const void *d_dests, int32_t ray_stride, int32_t n, void *d_rgb_out,
                                     void *stream, uint64_t counts[3] = nullptr) {
         rt_params p = params();

@@ -571,6 +571,63 @@ class Scene:
                                             C.c_void_p(within.data_ptr()), self._stream_ptr(stream)))
         return within[:n]
 
+    @staticmethod
+    def _inside_axis(name: str, axis) -> int:
+        if not isinstance(axis, int) or isinstance(axis, bool) or axis < _capi.AXIS_POS_X or axis > _capi.AXIS_NEG_Z:
+            raise ValueError(f"{name}: axis must be an int in [0, 5] (+x, -x, +y, -y, +z, -z), not {axis!r}")
+        return axis
+
+    def point_inside_device(self, points, axis: int = _capi.AXIS_POS_Z, crossings: bool = False, count=None, out=None, stream=None):
+        """rt_point_inside_device: inside[n] uint8, the parity of the number of candidate triangles the half line
+        from the point along `axis` (0..5: +x, -x, +y, -y, +z, -z) crosses (include/raytracert.h states the
+        arithmetic; it means something on a closed mesh only). points, count and stream as closest_point_device.
+        With crossings also crossings[n] int32, the number itself. out: a (>= n,) uint8 tensor to write into, or
+        with crossings an (inside, crossings) pair."""
+        import torch
+        name = "point_inside_device"
+        axis = self._inside_axis(name, axis)
+        n, stride = self._device_rays(name, "closest_point", points, points, ("points", "points"))
+        cnt = self._device_count(name, count)
+        if crossings and out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
+            raise ValueError(f"{name}: with crossings, out must be an (inside, crossings) pair")
+        out_in = out[0] if (crossings and out is not None) else out
+        inside = self._device_out(name, out_in, n, torch.uint8, (), 0, count is not None)
+        cr = self._device_out(name, None if out is None else out[1], n, torch.int32, (), 0, count is not None) if crossings else None
+        check(lib().rt_point_inside_device(self._h, C.c_void_p(points.data_ptr()), stride, n, cnt, axis, 0,
+                                           C.c_void_p(inside.data_ptr()), None if cr is None else C.c_void_p(cr.data_ptr()),
+                                           self._stream_ptr(stream)))
+        return (inside[:n], cr[:n]) if crossings else inside[:n]
+
+    def signed_distance_device(self, points, rmax=None, axis: int = _capi.AXIS_POS_Z, count=None, out=None,
+                               want_points: bool = False, stream=None):
+        """rt_signed_distance_device: closest_point_device's record with the distance negative where the point is
+        inside (point_inside_device along `axis`); a miss inside is (-1, -inf, 0, 0). Arguments as
+        closest_point_device. Returns (triangle[n] int32, distance[n] float32, st[n, 2] float32, inside[n] uint8)
+        and with want_points also point[n, 3]. out: the (>= n, 4) int32 record tensor to write into, or with
+        want_points a (records, points) pair."""
+        import torch
+        name = "signed_distance_device"
+        axis = self._inside_axis(name, axis)
+        n, stride = self._device_rays(name, "closest_point", points, points, ("points", "points"))
+        cnt = self._device_count(name, count)
+        rad = self._device_bound(name, "rmax", rmax, n)
+        if want_points and out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
+            raise ValueError(f"{name}: with want_points, out must be a (records, points) pair")
+        out_rec = out[0] if (want_points and out is not None) else out
+        rec = self._device_out(name, out_rec, n, torch.int32, (4,), 0, False)
+        if out_rec is None and count is not None:      # entries a device count leaves unwritten: the miss record
+            rec[:, 0], rec[:, 1], rec[:, 2:] = -1, 0x7F800000, 0      # (device fills: no host copy)
+        if rec.data_ptr() % _capi.HIT_BYTES:
+            raise ValueError(f"{name}: the record tensor must be 16-byte aligned")
+        pts = self._device_out(name, None if out is None else out[1], n, torch.float32, (3,), 0.0, count is not None) if want_points else None
+        inside = self._device_out(name, None, n, torch.uint8, (), 0, count is not None)
+        check(lib().rt_signed_distance_device(self._h, C.c_void_p(points.data_ptr()), stride, n, cnt, rad, axis, 0,
+                                              C.c_void_p(rec.data_ptr()), None if pts is None else C.c_void_p(pts.data_ptr()),
+                                              C.c_void_p(inside.data_ptr()), self._stream_ptr(stream)))
+        f = rec[:n].view(torch.float32)
+        res = (rec[:n, 0], f[:, 1], f[:, 2:4], inside[:n])
+        return res + (pts[:n],) if want_points else res
+
     def closest_point(self, points, rmax=None):
         """rt_closest_point for numpy arrays: returns (triangle[n] int32, distance[n] float32, st[n, 2] float32,
         point[n, 3] float32), closest_point_device's bits. rmax: optional n search radii."""

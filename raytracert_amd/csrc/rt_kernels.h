@@ -242,6 +242,14 @@ void launch_near_query(const DevScene &s, bool count_all, const void *pts, int32
 // mode of the same walk; k_point_any_query over every triangle).
 void launch_within_query(const DevScene &s, const void *pts, int32_t point_stride, int32_t n, const int32_t *d_count,
                          const float *d_rmax, uint8_t *within, hipStream_t stream);
+// Inside device query (rt_point_inside_device, rt_signed_distance_device): per point the number of candidate
+// triangles that cover it in the projection along `axis` (0..5: +x, -x, +y, -y, +z, -z) and lie above it.
+// xyz / tri_v: the scene's vertices and triangles on the device, what the records in s were built from.
+// inside[n] (bytes, the count's parity) and crossings[n] may each be null; hit (n 16-byte records, may be
+// null): the distance of a point with an odd count gets its sign bit set. d_count as launch_query_rays. The
+// tree walk (k_bvh_inside) and the loop over every triangle (k_inside) give the same counts.
+void launch_inside_query(const DevScene &s, const float *xyz, const uint32_t *tri_v, const void *pts, int32_t point_stride, int32_t n,
+                         const int32_t *d_count, int32_t axis, uint8_t *inside, int32_t *crossings, void *hit, hipStream_t stream);
 // launch_gen_rays from the caller's device arrays in either layout (rt_trace_rays_device)
 void launch_gen_rays_device(const void *org, const void *dst, int32_t ray_stride, int32_t n, const DevWork &w,
                             hipStream_t stream);

@@ -2012,6 +2012,189 @@ __global__ __launch_bounds__(kBlock) void k_point_query(const TriRec *__restrict
 }
 
 // ---------------------------------------------------------------------------------------------
+// Inside queries (rt_point_inside_device, rt_signed_distance_device): per query point the number of candidate
+// triangles (record normal not (0,0,0), the closest-point query's candidates) that the half line from the
+// point along a coordinate axis crosses, and its parity. include/raytracert.h states the arithmetic;
+// inside_eval is that statement op for op: the vertices are the scene's vertex array entries (xyz[tri_v[3 i + j]],
+// the same bits in every triangle that shares one), d_j = V_j - p in binary32, everything after in binary64.
+// The edge functions E are exact (two products of 24-bit factors and their difference's sign), so the cover
+// test is an exact even-odd test in the projection and a shared edge or vertex is claimed by exactly the
+// triangles that should claim it; the above test (num against det) rounds.
+// k_inside evaluates every triangle in index order; k_bvh_inside walks the tree and skips a child exactly
+// when the point lies outside its box on a projection axis, or beyond it along the direction. That test needs
+// no margin (DESIGN.md §7 "Inside and signed-distance queries"): fl32(x - y) has the sign of x - y, a
+// triangle that covers the point has 0 within the ranges of its X_j and Y_j, one that is above has some
+// Z_j > 0, and every box of the tree contains its triangles' vertices. What is not skipped is evaluated with
+// the same arithmetic and the result is a count, so the visiting order does not matter: no sort, the first
+// wanted child is entered and the others pushed (at most three per four-wide node, one per binary node).
+// ---------------------------------------------------------------------------------------------
+struct InsideQuery {
+    const float *xyz;           // the scene's vertices (3 per vertex) and
+    const uint32_t *tri_v;      // triangles (3 per triangle): what the current records were built from
+    int32_t axis;               // 0..5: +x, -x, +y, -y, +z, -z
+    uint8_t *inside;            // may be null (rt_signed_distance_device without d_inside_out)
+    int32_t *crossings;         // may be null
+    int4 *hit;                  // may be null; else the records whose distance takes the sign
+};
+
+__device__ __forceinline__ float pick3(float x, float y, float z, int i) { return i == 0 ? x : i == 1 ? y : z; }
+
+// The direction's axes: k along it, (a, b) across, sg = +1 / -1.
+struct InsideAxes {
+    int a, b, k;
+    float sg;
+    __device__ __forceinline__ explicit InsideAxes(int axis) : a(((axis >> 1) + 1) % 3), b(((axis >> 1) + 2) % 3), k(axis >> 1), sg((axis & 1) ? -1.0f : 1.0f) {}
+};
+
+__device__ __forceinline__ bool inside_edge(double X0, double Y0, double X1, double Y1, double &E) {
+    E = X0 * Y1 - Y0 * X1;   // both products exact: E has the exact sign
+    return (Y0 <= 0.0 && Y1 > 0.0 && E > 0.0) || (Y1 <= 0.0 && Y0 > 0.0 && E < 0.0);
+}
+
+// 1 when triangle idx is a candidate that covers p and is above it, else 0.
+__device__ __forceinline__ int inside_eval(const InsideQuery &q, const TriRec *__restrict__ tris, int idx, V3 p, const InsideAxes &ax) {
+    const float4 nq = reinterpret_cast<const float4 *>(tris + idx)[3];
+    if (nq.x == 0.0f && nq.y == 0.0f && nq.z == 0.0f) return 0;
+    const uint32_t *__restrict__ tv = q.tri_v + 3 * static_cast<size_t>(idx);
+    double X[3], Y[3], Z[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float *__restrict__ V = q.xyz + 3 * static_cast<size_t>(tv[j]);
+        const float dx = V[0] - p.x, dy = V[1] - p.y, dz = V[2] - p.z;
+        X[j] = static_cast<double>(pick3(dx, dy, dz, ax.a));
+        Y[j] = static_cast<double>(pick3(dx, dy, dz, ax.b));
+        Z[j] = static_cast<double>(ax.sg) * static_cast<double>(pick3(dx, dy, dz, ax.k));
+    }
+    double E0, E1, E2;
+    const int crossed = static_cast<int>(inside_edge(X[1], Y[1], X[2], Y[2], E0)) + static_cast<int>(inside_edge(X[2], Y[2], X[0], Y[0], E1)) +
+                        static_cast<int>(inside_edge(X[0], Y[0], X[1], Y[1], E2));
+    if (!(crossed & 1)) return 0;
+    const double det = (E0 + E1) + E2;
+    const double num = (E0 * Z[0] + E1 * Z[1]) + E2 * Z[2];
+    return ((det > 0.0 && num > 0.0) || (det < 0.0 && num < 0.0)) ? 1 : 0;
+}
+
+__device__ __forceinline__ bool inside_point_finite(V3 p) {
+    return fabsf(p.x) < INFINITY && fabsf(p.y) < INFINITY && fabsf(p.z) < INFINITY;   // (a NaN compares false)
+}
+
+__device__ __forceinline__ void store_inside(const InsideQuery &q, int j, int count) {
+    if (q.inside) q.inside[j] = static_cast<uint8_t>(count & 1);
+    if (q.crossings) q.crossings[j] = count;
+    if (q.hit && (count & 1)) reinterpret_cast<uint32_t *>(q.hit + j)[1] |= 0x80000000u;   // distance's sign bit
+}
+
+template <int W>
+__device__ __forceinline__ int bvh_inside_walk(const DevScene &sc, const InsideQuery &q, V3 p, bool walk, const InsideAxes &ax,
+                                               const LaneStack &stack, unsigned &tests, unsigned &visits) {
+    int count = 0;
+    // the always list: every lane
+    for (int i = 0; i < sc.n_always; ++i) count += inside_eval(q, sc.tris, static_cast<int>(sc.always[i]), p, ax);
+    tests += static_cast<unsigned>(max(sc.n_always, 0));
+    if (!walk) return 0;
+    const float pa = pick3(p.x, p.y, p.z, ax.a), pb = pick3(p.x, p.y, p.z, ax.b);
+    const float spk = ax.sg * pick3(p.x, p.y, p.z, ax.k);   // (times +1 or -1: exact)
+    int sp = 0;
+    int32_t ref = 0;
+    while (true) {
+        if (ref >= 0) {
+            ++visits;
+            if (W == 4) {
+                const float4 *np = reinterpret_cast<const float4 *>(sc.nodes4f + ref);
+                // the rows the column needs: lo and hi across, and the bound the direction leaves through
+                const float4 la = np[ax.a], ha = np[3 + ax.a], lb = np[ax.b], hb = np[3 + ax.b];
+                const float4 zk = np[ax.sg > 0.0f ? 3 + ax.k : ax.k];
+                const int4 ch = *reinterpret_cast<const int4 *>(np + 6);
+                const int32_t rc[4] = {ch.x, ch.y, ch.z, ch.w};
+                const float cla[4] = {la.x, la.y, la.z, la.w}, cha[4] = {ha.x, ha.y, ha.z, ha.w};
+                const float clb[4] = {lb.x, lb.y, lb.z, lb.w}, chb[4] = {hb.x, hb.y, hb.z, hb.w};
+                const float czk[4] = {zk.x, zk.y, zk.z, zk.w};
+                int32_t next = kBvhEmpty;
+#pragma unroll
+                for (int c = 3; c >= 0; --c) {   // (the lowest wanted slot is entered, the others pushed)
+                    const bool skip = pa < cla[c] || pa > cha[c] || pb < clb[c] || pb > chb[c] || spk > ax.sg * czk[c];
+                    if (!skip && rc[c] != kBvhEmpty) {
+                        if (next != kBvhEmpty) stack.push(sp, next);
+                        next = rc[c];
+                    }
+                }
+                if (next != kBvhEmpty) { ref = next; continue; }
+            } else {
+                const float4 *np = reinterpret_cast<const float4 *>(sc.nodes + ref);
+                const float4 q0 = np[0], q1 = np[1], q2 = np[2], q3 = np[3];
+                // BvhNode: lo0 = q0.xyz, hi0 = (q0.w, q1.x, q1.y), lo1 = (q1.z, q1.w, q2.x), hi1 = q2.yzw
+                const float l0a = pick3(q0.x, q0.y, q0.z, ax.a), h0a = pick3(q0.w, q1.x, q1.y, ax.a);
+                const float l0b = pick3(q0.x, q0.y, q0.z, ax.b), h0b = pick3(q0.w, q1.x, q1.y, ax.b);
+                const float l1a = pick3(q1.z, q1.w, q2.x, ax.a), h1a = pick3(q2.y, q2.z, q2.w, ax.a);
+                const float l1b = pick3(q1.z, q1.w, q2.x, ax.b), h1b = pick3(q2.y, q2.z, q2.w, ax.b);
+                const float z0 = ax.sg > 0.0f ? pick3(q0.w, q1.x, q1.y, ax.k) : pick3(q0.x, q0.y, q0.z, ax.k);
+                const float z1 = ax.sg > 0.0f ? pick3(q2.y, q2.z, q2.w, ax.k) : pick3(q1.z, q1.w, q2.x, ax.k);
+                const int32_t c0 = __float_as_int(q3.x), c1 = __float_as_int(q3.y);
+                const bool s0 = pa < l0a || pa > h0a || pb < l0b || pb > h0b || spk > ax.sg * z0;
+                const bool s1 = pa < l1a || pa > h1a || pb < l1b || pb > h1b || spk > ax.sg * z1;
+                const bool w0 = !s0 && c0 != kBvhEmpty, w1 = !s1 && c1 != kBvhEmpty;
+                if (w0 && w1) {
+                    stack.push(sp, c1);
+                    ref = c0;
+                    continue;
+                }
+                if (w0 || w1) { ref = w0 ? c0 : c1; continue; }
+            }
+        } else {
+            const uint32_t u = static_cast<uint32_t>(ref);
+            const int cnt = static_cast<int>((u >> kBvhCountShift) & kBvhCountMask);
+            const int first = static_cast<int>(u & ((1u << kBvhCountShift) - 1u));
+            // the original index, then tri_v and xyz: the leaf-ordered records do not hold V1, V2
+            for (int k = 0; k < cnt; ++k) count += inside_eval(q, sc.tris, static_cast<int>(sc.leaf_idx[first + k]), p, ax);
+            tests += static_cast<unsigned>(cnt);
+        }
+        if (sp == 0) break;
+        ref = stack.pop(sp);
+    }
+    return count;
+}
+
+template <int W, int kStride, bool kCount>
+__global__ __launch_bounds__(kBvhBlock) void k_bvh_inside(const DevScene sc, const void *__restrict__ pts, int n,
+                                                          const int32_t *__restrict__ d_count, const InsideQuery q) {
+    extern __shared__ int32_t lds_stack[];
+    const LaneStack stack = lane_stack(sc, lds_stack);
+    const InsideAxes ax(q.axis);
+    WorkTally<kCount> wt;
+    drive_queries(live_rays(d_count, n), 0, nullptr, [&](int j, int end) {
+        const bool active = j < end;
+        V3 p = mk(0, 0, 0);
+        bool walk = false;
+        if (active) {
+            p = load_ray_point<kStride>(pts, j);
+            walk = inside_point_finite(p);
+        }
+        wt.begin();
+        const int count = bvh_inside_walk<W>(sc, q, p, walk, ax, stack, wt.tests, wt.visits);
+        wt.end();
+        if (active) store_inside(q, j, count);
+    });
+    wt.flush(sc.work);
+}
+
+// The same over every triangle in index order (RT_ACCEL_BRUTE_FORCE, or no tree could be built).
+template <int kStride>
+__global__ __launch_bounds__(kBlock) void k_inside(const TriRec *__restrict__ tris, int nt, const void *__restrict__ pts, int n,
+                                                   const int32_t *__restrict__ d_count, const InsideQuery q) {
+    const int live = live_rays(d_count, n);
+    const int64_t base = static_cast<int64_t>(blockIdx.x) * kBlock;
+    if (base >= live) return;
+    if (base + threadIdx.x >= live) return;
+    const int j = static_cast<int>(base + threadIdx.x);
+    const V3 p = load_ray_point<kStride>(pts, j);
+    const InsideAxes ax(q.axis);
+    int count = 0;
+    if (inside_point_finite(p))
+        for (int i = 0; i < nt; ++i) count += inside_eval(q, tris, i, p, ax);
+    store_inside(q, j, count);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Nearest-triangle queries (rt_nearest_triangles_device, rt_within_radius_device): per query point the k
 // candidates with the smallest (dist2, index) among those with dist2 below the point's bound, as k rt_hit rows
 // in that order, or (kNearAny) only whether there is one. Candidate, dist2, s, t, c and the bound are the
@@ -5071,6 +5254,29 @@ void launch_point_query(const DevScene &s, const void *pts, int32_t point_stride
     const PointQuery q{d_rmax, static_cast<int4 *>(hit), point};
     if (point_stride == 4) launch_point_mode<4>(s, pts, n, d_count, q, stream);
     else launch_point_mode<3>(s, pts, n, d_count, q, stream);
+}
+
+namespace {
+template <int kStride>
+void launch_inside_mode(const DevScene &s0, const void *pts, int32_t n, const int32_t *d_count, const InsideQuery &q, hipStream_t stream) {
+    if (s0.use_bvh) {   // launch_point_mode's shape
+        const int W = s0.bvh_width == 4 ? 4 : 2;
+        const DevScene s = for_width(s0, W);
+        auto k = W == 4 ? (s.work ? k_bvh_inside<4, kStride, true> : k_bvh_inside<4, kStride, false>)
+                        : (s.work ? k_bvh_inside<2, kStride, true> : k_bvh_inside<2, kStride, false>);
+        hipLaunchKernelGGL(k, dim3(grid_bvh(n, s.bvh_grid)), dim3(kBvhBlock), bvh_lds(s), stream, s, pts, n, d_count, q);
+        return;
+    }
+    hipLaunchKernelGGL((k_inside<kStride>), dim3(grid_for(n)), dim3(kBlock), 0, stream, s0.tris, s0.nt, pts, n, d_count, q);
+}
+}  // namespace
+
+void launch_inside_query(const DevScene &s, const float *xyz, const uint32_t *tri_v, const void *pts, int32_t point_stride, int32_t n,
+                         const int32_t *d_count, int32_t axis, uint8_t *inside, int32_t *crossings, void *hit, hipStream_t stream) {
+    if (n <= 0) return;
+    const InsideQuery q{xyz, tri_v, axis, inside, crossings, static_cast<int4 *>(hit)};
+    if (point_stride == 4) launch_inside_mode<4>(s, pts, n, d_count, q, stream);
+    else launch_inside_mode<3>(s, pts, n, d_count, q, stream);
 }
 
 namespace {
