@@ -28,6 +28,8 @@
  *                         point, and whether it has one inside its radius)
  *   rt_point_inside_device / rt_signed_distance_device  (extensions: whether each query point is inside the
  *                         mesh, by crossing parity along an axis, and the closest-point record with that sign)
+ *   rt_box_overlap_device / rt_box_occupied_device  (extensions: the triangles that meet each axis-aligned query
+ *                         box, lowest indices first, and whether any does)
  *   rt_debug_trace       debug key 'd' (shoot + trace)     raytracing.cpp:493-510
  *                         (batched; also trace(o,d,lvl) at lvl 0, raytracing.h:30)
  *   rt_render_tile        the 'r'-key frame loop            main.cpp:340-411 (loop :355-395,
@@ -499,6 +501,52 @@ int rt_signed_distance_device(rt_scene *scene, const void *d_points, int32_t poi
                               const void *d_count, const void *d_rmax, int32_t axis, uint32_t flags,
                               void *d_hit_out, void *d_point_out /* may be NULL */,
                               void *d_inside_out /* may be NULL */, void *stream);
+/* The triangles that meet each axis-aligned query box, from one walk. d_lo and d_hi are the boxes' lower and upper
+ * corners, laid out as d_origins / d_dests of the ray entries (box_stride RT_RAYS_PACKED or RT_RAYS_PADDED, w
+ * ignored). d_count, stream, the ordering against updates, rebuilds, rt_scene_set_mesh and rt_scene_destroy, and rows
+ * at or past the live count (neither read nor written) as rt_closest_point_device. k is in [1, RT_MULTI_HIT_MAX].
+ * d_after (n x int32, 4-byte aligned, may be NULL): after_i, or -1 for every box when NULL.
+ * Let m be the number of candidates of box i that overlap it (below) and whose triangle index is greater than after_i.
+ * d_tris_out (n x k int32, box-major, 4-byte aligned): rows [i k, i k + min(m, k)) are the lowest of those indices in
+ * ascending order; the box's other rows are -1. d_nfound_out (n x int32, 4-byte aligned; may be NULL unless
+ * RT_BOX_COUNT_ALL): min(m, k), or with RT_BOX_COUNT_ALL m itself; the list is the same bytes whether or not the flag
+ * is set. A caller pages through a crowded box by passing the last index it received as after_i (the index-order
+ * analogue of stepping tmin).
+ *
+ * The definition. The candidates are rt_closest_point_device's: every triangle whose record normal is not (0,0,0).
+ * V_0, V_1, V_2 are the scene's current vertex array entries xyz[tri_v[3 t + j]]. A box with a NaN or infinite
+ * component, or with lo_a > hi_a on some axis, is empty: m = 0. lo == hi is a valid point box; a box is closed, so
+ * touching is overlap. No contraction anywhere. A candidate overlaps exactly when none of these tests separates it:
+ *   1. raw compares, no arithmetic: separated if on some axis a every V_j[a] > hi_a, or every V_j[a] < lo_a
+ *      (min_j V_j[a] > hi_a or max_j V_j[a] < lo_a)
+ *   2. c = (lo + hi) * 0.5f and h = (hi - lo) * 0.5f per component, v_j = V_j - c per component, all binary32;
+ *      from here on everything is binary64: v_j and h widened
+ *   3. the edges f_0 = v_1 - v_0, f_1 = v_2 - v_1, f_2 = v_0 - v_2; for each edge f and each axis a, with
+ *      (b, c) = ((a + 1) % 3, (a + 2) % 3):
+ *        p_j = f[b] * v_j[c] - f[c] * v_j[b]   (j = 0, 1, 2)        r = h[b] * |f[c]| + h[c] * |f[b]|
+ *      separated if every p_j > r, or every p_j < -r (min_j p_j > r or max_j p_j < -r)
+ *   4. n = f_0 x f_1, n[a] = f_0[b] * f_1[c] - f_0[c] * f_1[b];  d = (n[0] v_0[0] + n[1] v_0[1]) + n[2] v_0[2];
+ *      r = (h[0] |n[0]| + h[1] |n[1]|) + h[2] |n[2]|;  separated if d > r or d < -r
+ * Consequences: by step 1 an overlapping triangle's own box meets the query box, so a tree walk that skips a child
+ * exactly when lo_a > child_hi_a or hi_a < child_lo_a on some axis loses nothing and needs no margin: the result is
+ * the list of the loop over every triangle, on any builder, either tree width, after any refit. A NaN produced in
+ * steps 2 to 4 separates nothing. Coordinates are assumed small enough that hi - lo and V_j - c do not overflow.
+ * The verdict is exact (the closed triangle meets the closed box) wherever the binary32 centring is exact, for
+ * example on dyadic coordinates; elsewhere it is bracketed by the box shrunk and grown by 2^-18 of the largest
+ * coordinate magnitude, and within that band, at touching, it is deterministic but not guaranteed: a point box on a
+ * shared vertex may claim only some of the triangles around it.
+ * Errors in rt_nearest_triangles_device's order: RT_E_NODEV on a host-only scene before anything else; RT_E_ARG for a
+ * NULL scene, n < 0, a bad stride, NULL or misaligned arrays, k out of range, any flag but RT_BOX_COUNT_ALL, that flag
+ * with a NULL d_nfound_out, n * k above INT32_MAX; n == 0 returns RT_OK with nothing enqueued. */
+#define RT_BOX_COUNT_ALL (1u << 4)   /* d_nfound_out = every overlapping candidate past `after`, not min(m, k) */
+int rt_box_overlap_device(rt_scene *scene, const void *d_lo, const void *d_hi, int32_t box_stride, int32_t n,
+                          const void *d_count, const void *d_after /* n x int32, may be NULL */, uint32_t flags, int32_t k,
+                          void *d_tris_out /* n x k int32 */, void *d_nfound_out /* n x int32 */, void *stream);
+/* Whether anything meets the box: d_occupied_out[i] (n x uint8) is 1 when m > 0 (after_i = -1) and 0 otherwise; the
+ * walk leaves a box at its first overlapping candidate. flags must be 0 (RT_E_ARG otherwise). Everything else as the
+ * entry above. */
+int rt_box_occupied_device(rt_scene *scene, const void *d_lo, const void *d_hi, int32_t box_stride, int32_t n,
+                           const void *d_count, uint32_t flags, void *d_occupied_out /* n x uint8 */, void *stream);
 /* performRayTracing (raytracing.cpp:410-416) for rays in device memory: d_rgb_out[3*i..] (3n packed floats),
  * bit for bit rt_trace_rays' rgb_out. counts as in rt_trace_rays; non-NULL synchronises the stream. Uses
  * render pipeline 0's workspace (ordered against the frames that use it): returns after enqueueing when

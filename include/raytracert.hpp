@@ -246,6 +246,17 @@ class RayTracer {
         check(rt_signed_distance_device(scene_, d_points, point_stride, n, d_count, d_rmax, axis, flags, d_hit_out, d_point_out,
                                         d_inside_out, stream));
     }
+    // the triangles that meet each axis-aligned box, lowest indices first (rt_box_overlap_device: d_after n int32 or null,
+    // d_tris_out n x k int32, d_nfound_out n int32 or null; flags: RT_BOX_COUNT_ALL)
+    void box_overlap_device(const void *d_lo, const void *d_hi, int32_t box_stride, int32_t n, const void *d_count, const void *d_after,
+                            uint32_t flags, int32_t k, void *d_tris_out, void *d_nfound_out, void *stream) {
+        check(rt_box_overlap_device(scene_, d_lo, d_hi, box_stride, n, d_count, d_after, flags, k, d_tris_out, d_nfound_out, stream));
+    }
+    // whether a triangle meets each box (rt_box_occupied_device: d_occupied_out n x uint8; flags 0)
+    void box_occupied_device(const void *d_lo, const void *d_hi, int32_t box_stride, int32_t n, const void *d_count, uint32_t flags,
+                             void *d_occupied_out, void *stream) {
+        check(rt_box_occupied_device(scene_, d_lo, d_hi, box_stride, n, d_count, flags, d_occupied_out, stream));
+    }
     void perform_ray_tracing_device(const void *d_origins, const void *d_dests, int32_t ray_stride, int32_t n, void *d_rgb_out,
                                     void *stream, uint64_t counts[3] = nullptr) {
         rt_params p = params();

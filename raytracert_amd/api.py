@@ -628,6 +628,48 @@ class Scene:
         res = (rec[:n, 0], f[:, 1], f[:, 2:4], inside[:n])
         return res + (pts[:n],) if want_points else res
 
+    def box_overlap_device(self, lo, hi, k: int, after=None, count=None, count_all: bool = False, out=None, stream=None):
+        """rt_box_overlap_device: per axis-aligned box [lo, hi] (closed; include/raytracert.h states the arithmetic),
+        the k (1.._capi.MULTI_HIT_MAX) lowest indices of the candidate triangles that overlap it, ascending, from
+        one walk. lo / hi: contiguous CUDA float32 tensors (n, 3) or (n, 4) (w ignored); count and stream as
+        closest_point_device. after: an optional CUDA int32 tensor of n elements; only triangles with a greater
+        index are listed and counted (pass the last index received to page through a crowded box). Returns
+        (tris[n, k] int32, nfound[n] int32): rows past a box's triangles hold -1; nfound is the number of rows that
+        hold a triangle, or with count_all the number of overlapping candidates past `after` (which may exceed k).
+        A box with a non-finite component or lo > hi on an axis is empty. out: a (tris, nfound) pair to write
+        into, (>= n, k) int32 and (>= n,) int32; the result is then views of them."""
+        import torch
+        name = "box_overlap_device"
+        if not isinstance(k, int) or isinstance(k, bool) or k < 1 or k > _capi.MULTI_HIT_MAX:
+            raise ValueError(f"{name}: k must be an int in [1, {_capi.MULTI_HIT_MAX}], not {k!r}")
+        n, stride = self._device_rays(name, "no host method", lo, hi, ("lo", "hi"))
+        cnt = self._device_count(name, count)
+        if after is not None and (not isinstance(after, torch.Tensor) or not after.is_cuda or after.device.index != self.device
+                                  or after.dtype != torch.int32 or after.dim() != 1 or not after.is_contiguous() or after.shape[0] < n):
+            raise ValueError(f"{name}: after must be a contiguous CUDA int32 tensor of shape (>= {n},) on the scene's device")
+        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
+            raise ValueError(f"{name}: out must be a (tris, nfound) pair")
+        tris = self._device_out(name, None if out is None else out[0], n, torch.int32, (k,), -1, count is not None)
+        nf = self._device_out(name, None if out is None else out[1], n, torch.int32, (), 0, count is not None)
+        check(lib().rt_box_overlap_device(self._h, C.c_void_p(lo.data_ptr()), C.c_void_p(hi.data_ptr()), stride, n, cnt,
+                                          None if after is None else C.c_void_p(after.data_ptr()),
+                                          _capi.BOX_COUNT_ALL if count_all else 0, k, C.c_void_p(tris.data_ptr()),
+                                          C.c_void_p(nf.data_ptr()), self._stream_ptr(stream)))
+        return tris[:n], nf[:n]
+
+    def box_occupied_device(self, lo, hi, count=None, out=None, stream=None):
+        """rt_box_occupied_device: occupied[n] uint8, 1 where a candidate triangle overlaps the box [lo, hi] (where
+        box_overlap_device lists a triangle), else 0; the walk leaves a box at the first such triangle. lo, hi,
+        count and stream as box_overlap_device; out: a (>= n,) uint8 tensor to write into."""
+        import torch
+        name = "box_occupied_device"
+        n, stride = self._device_rays(name, "no host method", lo, hi, ("lo", "hi"))
+        cnt = self._device_count(name, count)
+        occ = self._device_out(name, out, n, torch.uint8, (), 0, count is not None)
+        check(lib().rt_box_occupied_device(self._h, C.c_void_p(lo.data_ptr()), C.c_void_p(hi.data_ptr()), stride, n, cnt, 0,
+                                           C.c_void_p(occ.data_ptr()), self._stream_ptr(stream)))
+        return occ[:n]
+
     def closest_point(self, points, rmax=None):
         """rt_closest_point for numpy arrays: returns (triangle[n] int32, distance[n] float32, st[n, 2] float32,
         point[n, 3] float32), closest_point_device's bits. rmax: optional n search radii."""

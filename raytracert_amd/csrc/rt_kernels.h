@@ -250,6 +250,17 @@ void launch_within_query(const DevScene &s, const void *pts, int32_t point_strid
 // tree walk (k_bvh_inside) and the loop over every triangle (k_inside) give the same counts.
 void launch_inside_query(const DevScene &s, const float *xyz, const uint32_t *tri_v, const void *pts, int32_t point_stride, int32_t n,
                          const int32_t *d_count, int32_t axis, uint8_t *inside, int32_t *crossings, void *hit, hipStream_t stream);
+// Box-overlap device query (rt_box_overlap_device): per box (lo[n], hi[n] in the ray entries' layouts) the k lowest
+// indices above after[i] (null: -1) of the candidate triangles that overlap it, ascending, as tris_out[n][k]
+// (rows past the list: -1), and nfound[n] when not null: the rows that hold a triangle, or with count_all every
+// overlapping candidate above after[i]. xyz / tri_v as launch_inside_query, d_count as launch_query_rays. The
+// tree walk (k_bvh_box) and the loop over every triangle (k_box) give the same bytes.
+void launch_box_query(const DevScene &s, const float *xyz, const uint32_t *tri_v, bool count_all, const void *lo, const void *hi,
+                      int32_t box_stride, int32_t n, const int32_t *d_count, const int32_t *after, int32_t k, int32_t *tris_out,
+                      int32_t *nfound, hipStream_t stream);
+// rt_box_occupied_device: occupied[n] = 1 when a candidate overlaps the box, else 0 (the any mode of the same walk).
+void launch_box_occupied(const DevScene &s, const float *xyz, const uint32_t *tri_v, const void *lo, const void *hi, int32_t box_stride,
+                         int32_t n, const int32_t *d_count, uint8_t *occupied, hipStream_t stream);
 // launch_gen_rays from the caller's device arrays in either layout (rt_trace_rays_device)
 void launch_gen_rays_device(const void *org, const void *dst, int32_t ray_stride, int32_t n, const DevWork &w,
                             hipStream_t stream);

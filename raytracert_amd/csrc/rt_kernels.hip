@@ -2195,6 +2195,286 @@ __global__ __launch_bounds__(kBlock) void k_inside(const TriRec *__restrict__ tr
 }
 
 // ---------------------------------------------------------------------------------------------
+// Box-overlap queries (rt_box_overlap_device, rt_box_occupied_device): per axis-aligned query box the candidate
+// triangles (record normal not (0,0,0)) that meet it, as the k lowest indices above the box's `after` in
+// ascending order, optionally their number, or (kBoxAny) only whether there is one. include/raytracert.h states
+// the arithmetic; box_eval is that statement op for op: the vertices are the scene's vertex array entries, step 1
+// compares them raw with the box's bounds, step 2 centres in binary32, steps 3 and 4 (the nine edge axes and the
+// triangle's plane of the separating-axis test) are binary64. "min_j p_j > r" is written as all three compares,
+// so a NaN separates nothing.
+// k_box evaluates every triangle in index order; k_bvh_box walks the tree and skips a child exactly when the
+// query box and the child's box are disjoint on some axis. That needs no margin (DESIGN.md §7 "Box-overlap
+// queries"): step 1 makes a triangle that overlaps have, on every axis, a vertex coordinate at or below hi and
+// one at or above lo, and every box of the tree contains its triangles' vertices. What is not skipped is
+// evaluated with the same arithmetic and the result is a set, so the visiting order does not matter: no sort,
+// the first wanted child is entered and the others pushed.
+// The list is BoxList: k ascending 32-bit indices per lane in dynamic LDS behind the traversal stack, laid out
+// as MultiList is ([slot][block lane]); an index needs no distance, so a slot is 4 bytes, not a 64-bit key. A
+// walk meets a triangle at most once, so no index comes twice. A triangle whose index is at or below `after`,
+// or (list full, not counting all) above the k-th entry, is passed over before its vertices are loaded.
+// ---------------------------------------------------------------------------------------------
+enum : int { kBoxList = 0, kBoxListAll = 1, kBoxAny = 2 };
+struct BoxQuery {
+    const float *xyz;           // the scene's vertices (3 per vertex) and
+    const uint32_t *tri_v;      // triangles (3 per triangle): what the current records were built from
+    const void *hi;             // the boxes' upper corners (the lower ones travel as the kernel's pts)
+    const int32_t *after;       // per box, or null (-1)
+    int32_t k;
+    int32_t *tris_out;          // [n][k] (list modes)
+    int32_t *nfound;            // [n], or null
+    uint8_t *occupied;          // [n] (kBoxAny)
+};
+
+struct BoxList {
+    int32_t *idx;               // this lane's slot 0; slot i is idx[i * width]
+    int width, k;
+    int cnt = 0, total = 0;     // indices held; overlapping candidates above `after` met
+    int bound = INT32_MAX;      // the k-th entry once the list is full: nothing above it can enter
+    __device__ __forceinline__ void admit(int t) {
+        ++total;
+        if (t > bound) return;
+        int i = min(cnt, k - 1);   // the slot that opens: the end of a list not yet full, else the last (its entry drops out)
+        while (i > 0) {            // compare-shift
+            const int32_t prev = idx[(i - 1) * width];
+            if (prev < t) break;
+            idx[i * width] = prev;
+            --i;
+        }
+        idx[i * width] = t;
+        cnt = min(cnt + 1, k);
+        if (cnt == k) bound = idx[(k - 1) * width];
+    }
+};
+
+// One query box: its corners, and step 2's centre and half extent (binary32).
+struct QBox {
+    V3 lo, hi, c, h;
+};
+
+// false for an empty box: a NaN or infinite component, or lo > hi on some axis.
+__device__ __forceinline__ bool make_qbox(V3 lo, V3 hi, QBox &b) {
+    b.lo = lo;
+    b.hi = hi;
+    b.c = mk((lo.x + hi.x) * 0.5f, (lo.y + hi.y) * 0.5f, (lo.z + hi.z) * 0.5f);
+    b.h = mk((hi.x - lo.x) * 0.5f, (hi.y - lo.y) * 0.5f, (hi.z - lo.z) * 0.5f);
+    return inside_point_finite(lo) && inside_point_finite(hi) && lo.x <= hi.x && lo.y <= hi.y && lo.z <= hi.z;
+}
+
+// Whether triangle idx is a candidate that overlaps the box.
+__device__ __forceinline__ bool box_eval(const BoxQuery &q, const TriRec *__restrict__ tris, int idx, const QBox &b) {
+    const float4 nq = reinterpret_cast<const float4 *>(tris + idx)[3];
+    if (nq.x == 0.0f && nq.y == 0.0f && nq.z == 0.0f) return false;
+    const uint32_t *__restrict__ tv = q.tri_v + 3 * static_cast<size_t>(idx);
+    const float *__restrict__ A = q.xyz + 3 * static_cast<size_t>(tv[0]);
+    const float *__restrict__ B = q.xyz + 3 * static_cast<size_t>(tv[1]);
+    const float *__restrict__ Cv = q.xyz + 3 * static_cast<size_t>(tv[2]);
+    const float V[3][3] = {{A[0], A[1], A[2]}, {B[0], B[1], B[2]}, {Cv[0], Cv[1], Cv[2]}};
+    const float lo[3] = {b.lo.x, b.lo.y, b.lo.z}, hi[3] = {b.hi.x, b.hi.y, b.hi.z};
+    // 1: raw compares (most leaf triangles end here, before any binary64)
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        if (V[0][a] > hi[a] && V[1][a] > hi[a] && V[2][a] > hi[a]) return false;
+        if (V[0][a] < lo[a] && V[1][a] < lo[a] && V[2][a] < lo[a]) return false;
+    }
+    // 2: centred in binary32, then widened
+    const float c[3] = {b.c.x, b.c.y, b.c.z};
+    const double h[3] = {static_cast<double>(b.h.x), static_cast<double>(b.h.y), static_cast<double>(b.h.z)};
+    double v[3][3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) v[j][a] = static_cast<double>(V[j][a] - c[a]);
+    double f[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        f[0][a] = v[1][a] - v[0][a];
+        f[1][a] = v[2][a] - v[1][a];
+        f[2][a] = v[0][a] - v[2][a];
+    }
+    // 3: the nine edge axes (straight-line: a triangle that passes step 1 mostly needs them all, and its
+    // neighbours in the wave would wait for it anyway)
+    bool sep = false;
+#pragma unroll
+    for (int e = 0; e < 3; ++e)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const int bb = (a + 1) % 3, cc = (a + 2) % 3;
+            const double p0 = f[e][bb] * v[0][cc] - f[e][cc] * v[0][bb];
+            const double p1 = f[e][bb] * v[1][cc] - f[e][cc] * v[1][bb];
+            const double p2 = f[e][bb] * v[2][cc] - f[e][cc] * v[2][bb];
+            const double r = h[bb] * fabs(f[e][cc]) + h[cc] * fabs(f[e][bb]);
+            sep |= (p0 > r && p1 > r && p2 > r) || (p0 < -r && p1 < -r && p2 < -r);
+        }
+    // 4: the triangle's plane
+    double nn[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const int bb = (a + 1) % 3, cc = (a + 2) % 3;
+        nn[a] = f[0][bb] * f[1][cc] - f[0][cc] * f[1][bb];
+    }
+    const double d = (nn[0] * v[0][0] + nn[1] * v[0][1]) + nn[2] * v[0][2];
+    const double r = (h[0] * fabs(nn[0]) + h[1] * fabs(nn[1])) + h[2] * fabs(nn[2]);
+    return !(sep || d > r || d < -r);
+}
+
+// One triangle of a walk: the index filter, then the evaluation. kBoxAny: found is set and nothing else changes.
+template <int kMode>
+__device__ __forceinline__ void box_visit(const BoxQuery &q, const TriRec *__restrict__ tris, int idx, const QBox &b, int after, BoxList &bl,
+                                          bool &found) {
+    if (kMode == kBoxAny) {
+        if (!found && box_eval(q, tris, idx, b)) found = true;
+        return;
+    }
+    if (idx <= after || (kMode == kBoxList && idx > bl.bound)) return;
+    if (box_eval(q, tris, idx, b)) bl.admit(idx);
+}
+
+template <int W, int kMode>
+__device__ __forceinline__ void bvh_box_walk(const DevScene &sc, const BoxQuery &q, const QBox &b, bool walk, int after, BoxList &bl,
+                                             bool &found, const LaneStack &stack, unsigned &tests, unsigned &visits) {
+    // the always list: every lane (one whose box is empty takes nothing from it)
+    for (int i = 0; i < sc.n_always; ++i)
+        if (walk) box_visit<kMode>(q, sc.tris, static_cast<int>(sc.always[i]), b, after, bl, found);
+    tests += static_cast<unsigned>(max(sc.n_always, 0));
+    if (!walk || found) return;
+    int sp = 0;
+    int32_t ref = 0;
+    while (true) {
+        if (ref >= 0) {
+            ++visits;
+            if (W == 4) {
+                const float4 *np = reinterpret_cast<const float4 *>(sc.nodes4f + ref);
+                const float4 lx = np[0], ly = np[1], lz = np[2], hx = np[3], hy = np[4], hz = np[5];
+                const int4 ch = *reinterpret_cast<const int4 *>(np + 6);
+                const int32_t rc[4] = {ch.x, ch.y, ch.z, ch.w};
+                const float blx[4] = {lx.x, lx.y, lx.z, lx.w}, bly[4] = {ly.x, ly.y, ly.z, ly.w}, blz[4] = {lz.x, lz.y, lz.z, lz.w};
+                const float bhx[4] = {hx.x, hx.y, hx.z, hx.w}, bhy[4] = {hy.x, hy.y, hy.z, hy.w}, bhz[4] = {hz.x, hz.y, hz.z, hz.w};
+                int32_t next = kBvhEmpty;
+#pragma unroll
+                for (int c = 3; c >= 0; --c) {   // (the lowest wanted slot is entered, the others pushed)
+                    const bool skip = b.lo.x > bhx[c] || b.hi.x < blx[c] || b.lo.y > bhy[c] || b.hi.y < bly[c] || b.lo.z > bhz[c] ||
+                                      b.hi.z < blz[c];
+                    if (!skip && rc[c] != kBvhEmpty) {
+                        if (next != kBvhEmpty) stack.push(sp, next);
+                        next = rc[c];
+                    }
+                }
+                if (next != kBvhEmpty) { ref = next; continue; }
+            } else {
+                const float4 *np = reinterpret_cast<const float4 *>(sc.nodes + ref);
+                const float4 q0 = np[0], q1 = np[1], q2 = np[2], q3 = np[3];
+                // BvhNode: lo0 = q0.xyz, hi0 = (q0.w, q1.x, q1.y), lo1 = (q1.z, q1.w, q2.x), hi1 = q2.yzw
+                const bool s0 = b.lo.x > q0.w || b.hi.x < q0.x || b.lo.y > q1.x || b.hi.y < q0.y || b.lo.z > q1.y || b.hi.z < q0.z;
+                const bool s1 = b.lo.x > q2.y || b.hi.x < q1.z || b.lo.y > q2.z || b.hi.y < q1.w || b.lo.z > q2.w || b.hi.z < q2.x;
+                const int32_t c0 = __float_as_int(q3.x), c1 = __float_as_int(q3.y);
+                const bool w0 = !s0 && c0 != kBvhEmpty, w1 = !s1 && c1 != kBvhEmpty;
+                if (w0 && w1) {
+                    stack.push(sp, c1);
+                    ref = c0;
+                    continue;
+                }
+                if (w0 || w1) { ref = w0 ? c0 : c1; continue; }
+            }
+        } else {
+            const uint32_t u = static_cast<uint32_t>(ref);
+            const int cnt = static_cast<int>((u >> kBvhCountShift) & kBvhCountMask);
+            const int first = static_cast<int>(u & ((1u << kBvhCountShift) - 1u));
+            // the original index, then tri_v and xyz: the leaf-ordered records do not hold V1, V2
+            if (kMode == kBoxAny) {
+                for (int k = 0; k < cnt && !found; ++k) {
+                    box_visit<kMode>(q, sc.tris, static_cast<int>(sc.leaf_idx[first + k]), b, after, bl, found);
+                    ++tests;
+                }
+                if (found) return;
+            } else {
+                for (int k = 0; k < cnt; ++k) box_visit<kMode>(q, sc.tris, static_cast<int>(sc.leaf_idx[first + k]), b, after, bl, found);
+                tests += static_cast<unsigned>(cnt);
+            }
+        }
+        if (sp == 0) break;
+        ref = stack.pop(sp);
+    }
+}
+
+// The rows of one box: the list in order, then -1.
+template <int kMode>
+__device__ __forceinline__ void store_box(const BoxList &bl, int j, const BoxQuery &q) {
+    const size_t row0 = static_cast<size_t>(j) * static_cast<size_t>(bl.k);
+    auto entry = [&](int i) { return i < bl.cnt ? bl.idx[i * bl.width] : -1; };
+    if ((bl.k & 3) == 0 && (reinterpret_cast<uintptr_t>(q.tris_out) & 15) == 0) {   // (wave-uniform) rows of whole 16-byte stores
+        int4 *row = reinterpret_cast<int4 *>(q.tris_out + row0);
+        for (int i = 0; i < bl.k; i += 4) row[i >> 2] = make_int4(entry(i), entry(i + 1), entry(i + 2), entry(i + 3));
+    } else {
+        for (int i = 0; i < bl.k; ++i) q.tris_out[row0 + i] = entry(i);
+    }
+    if (q.nfound) q.nfound[j] = kMode == kBoxListAll ? bl.total : bl.cnt;
+}
+
+template <int kStride>
+__device__ __forceinline__ bool load_qbox(const void *__restrict__ lo, const BoxQuery &q, int j, QBox &b, int &after) {
+    after = q.after ? q.after[j] : -1;
+    return make_qbox(load_ray_point<kStride>(lo, j), load_ray_point<kStride>(q.hi, j), b);
+}
+
+template <int W, int kStride, int kMode, bool kCount>
+__global__ __launch_bounds__(kBvhBlock) void k_bvh_box(const DevScene sc, const void *__restrict__ lo, int n,
+                                                       const int32_t *__restrict__ d_count, const BoxQuery q) {
+    extern __shared__ int32_t lds_stack[];
+    const LaneStack stack = lane_stack(sc, lds_stack);
+    int32_t *const lists = lds_stack + max(sc.lds_stack, 1) * kBvhBlock;
+    WorkTally<kCount> wt;
+    drive_queries(live_rays(d_count, n), 0, nullptr, [&](int j, int end) {
+        const bool active = j < end;
+        QBox b;
+        b.lo = b.hi = b.c = b.h = mk(0, 0, 0);
+        int after = -1;
+        bool walk = false;
+        if (active) walk = load_qbox<kStride>(lo, q, j, b, after);
+        BoxList bl;
+        bl.idx = lists + threadIdx.x;   // (kBoxAny: never touched, and the launch has no LDS for it)
+        bl.width = kBvhBlock;
+        bl.k = kMode == kBoxAny ? 0 : q.k;
+        bool found = false;
+        wt.begin();
+        bvh_box_walk<W, kMode>(sc, q, b, walk, after, bl, found, stack, wt.tests, wt.visits);
+        wt.end();
+        if (!active) return;
+        if (kMode == kBoxAny) q.occupied[j] = found ? 1 : 0;
+        else store_box<kMode>(bl, j, q);
+    });
+    wt.flush(sc.work);
+}
+
+// The same over every triangle in index order (RT_ACCEL_BRUTE_FORCE, or no tree could be built).
+template <int kStride, int kMode>
+__global__ __launch_bounds__(kBlock) void k_box(const TriRec *__restrict__ tris, int nt, const void *__restrict__ lo, int n,
+                                                const int32_t *__restrict__ d_count, const BoxQuery q) {
+    extern __shared__ int32_t lds_stack[];   // the lists alone
+    const int live = live_rays(d_count, n);
+    const int64_t base = static_cast<int64_t>(blockIdx.x) * kBlock;
+    if (base >= live) return;
+    const bool active = base + threadIdx.x < live;
+    const int j = active ? static_cast<int>(base + threadIdx.x) : 0;
+    QBox b;
+    b.lo = b.hi = b.c = b.h = mk(0, 0, 0);
+    int after = -1;
+    bool walk = false;
+    if (active) walk = load_qbox<kStride>(lo, q, j, b, after);
+    BoxList bl;
+    bl.idx = lds_stack + threadIdx.x;
+    bl.width = kBlock;
+    bl.k = kMode == kBoxAny ? 0 : q.k;
+    bool found = !walk;         // (kBoxAny) a lane whose box is empty has nothing to look for
+    for (int i = 0; i < nt; ++i) {
+        if (kMode == kBoxAny && (i & 15) == 0 && __all(found)) break;
+        if (walk) box_visit<kMode>(q, tris, i, b, after, bl, found);
+    }
+    if (!active) return;
+    if (kMode == kBoxAny) q.occupied[j] = walk && found ? 1 : 0;
+    else store_box<kMode>(bl, j, q);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Nearest-triangle queries (rt_nearest_triangles_device, rt_within_radius_device): per query point the k
 // candidates with the smallest (dist2, index) among those with dist2 below the point's bound, as k rt_hit rows
 // in that order, or (kNearAny) only whether there is one. Candidate, dist2, s, t, c and the bound are the
@@ -5277,6 +5557,48 @@ void launch_inside_query(const DevScene &s, const float *xyz, const uint32_t *tr
     const InsideQuery q{xyz, tri_v, axis, inside, crossings, static_cast<int4 *>(hit)};
     if (point_stride == 4) launch_inside_mode<4>(s, pts, n, d_count, q, stream);
     else launch_inside_mode<3>(s, pts, n, d_count, q, stream);
+}
+
+namespace {
+// LDS of the box kernels' lists: k 32-bit indices per lane
+inline size_t box_lds(int k, int lanes) { return sizeof(int32_t) * lanes * static_cast<size_t>(k); }
+template <int kStride, int kMode>
+void launch_box_mode(const DevScene &s0, const void *lo, int32_t n, const int32_t *d_count, const BoxQuery &q, hipStream_t stream) {
+    constexpr bool kList = kMode != kBoxAny;
+    if (s0.use_bvh) {   // launch_near_mode's shape; the lists' LDS follows the stack's
+        const int W = s0.bvh_width == 4 ? 4 : 2;
+        const DevScene s = for_width(s0, W);
+        auto k = W == 4 ? (s.work ? k_bvh_box<4, kStride, kMode, true> : k_bvh_box<4, kStride, kMode, false>)
+                        : (s.work ? k_bvh_box<2, kStride, kMode, true> : k_bvh_box<2, kStride, kMode, false>);
+        hipLaunchKernelGGL(k, dim3(grid_bvh(n, s.bvh_grid)), dim3(kBvhBlock), bvh_lds(s) + (kList ? box_lds(q.k, kBvhBlock) : 0), stream, s,
+                           lo, n, d_count, q);
+        return;
+    }
+    hipLaunchKernelGGL((k_box<kStride, kMode>), dim3(grid_for(n)), dim3(kBlock), kList ? box_lds(q.k, kBlock) : 0, stream, s0.tris, s0.nt,
+                       lo, n, d_count, q);
+}
+template <int kMode>
+void launch_box_stride(const DevScene &s, const void *lo, int32_t box_stride, int32_t n, const int32_t *d_count, const BoxQuery &q,
+                       hipStream_t stream) {
+    if (box_stride == 4) launch_box_mode<4, kMode>(s, lo, n, d_count, q, stream);
+    else launch_box_mode<3, kMode>(s, lo, n, d_count, q, stream);
+}
+}  // namespace
+
+void launch_box_query(const DevScene &s, const float *xyz, const uint32_t *tri_v, bool count_all, const void *lo, const void *hi,
+                      int32_t box_stride, int32_t n, const int32_t *d_count, const int32_t *after, int32_t k, int32_t *tris_out,
+                      int32_t *nfound, hipStream_t stream) {
+    if (n <= 0) return;
+    const BoxQuery q{xyz, tri_v, hi, after, k, tris_out, nfound, nullptr};
+    if (count_all) launch_box_stride<kBoxListAll>(s, lo, box_stride, n, d_count, q, stream);
+    else launch_box_stride<kBoxList>(s, lo, box_stride, n, d_count, q, stream);
+}
+
+void launch_box_occupied(const DevScene &s, const float *xyz, const uint32_t *tri_v, const void *lo, const void *hi, int32_t box_stride,
+                         int32_t n, const int32_t *d_count, uint8_t *occupied, hipStream_t stream) {
+    if (n <= 0) return;
+    const BoxQuery q{xyz, tri_v, hi, nullptr, 0, nullptr, nullptr, occupied};
+    launch_box_stride<kBoxAny>(s, lo, box_stride, n, d_count, q, stream);
 }
 
 namespace {
