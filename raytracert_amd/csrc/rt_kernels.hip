@@ -363,6 +363,133 @@ __device__ __forceinline__ LaneStack lane_stack(const DevScene &sc, int32_t *lds
     return st;
 }
 
+// The dynamic LDS behind the stack's part: the per-lane lists of the kernels that keep one.
+__device__ __forceinline__ int32_t *lds_after_stack(const DevScene &sc, int32_t *lds) { return lds + max(sc.lds_stack, 1) * kBvhBlock; }
+
+// The exchange of the four-wide walks' sorting network (Bvh4F: a node's hit children are sorted by entry
+// distance, the nearest is visited next and the others are pushed farthest first).
+__device__ __forceinline__ void cswap(float &ta, int32_t &ra, float &tb, int32_t &rb) {
+    const bool sw = tb < ta;
+    const float t = sw ? tb : ta;
+    const int32_t r = sw ? rb : ra;
+    tb = sw ? ta : tb;
+    rb = sw ? ra : rb;
+    ta = t;
+    ra = r;
+}
+
+__device__ __forceinline__ float pick3(float x, float y, float z, int i) { return i == 0 ? x : i == 1 ? y : z; }
+
+// One child's box as a walk's child test sees it: lo(a) and hi(a) are its bounds on axis a (binary: bound(a, upper)
+// is the one of the two that `upper` names). A four-wide node (Bvh4F) is six rows of one float per slot, lo x, y, z
+// then hi x, y, z, which bvh_walk loads whole, as six 16-byte rows that the four slots share; the view is slot c of
+// them, for constant axes. A binary node (BvhNode) is loaded whole too, and its view also takes an axis that is
+// known only when the kernel runs.
+struct ChildBox4 {
+    const float4 (&rows)[6];
+    int c;
+    __device__ __forceinline__ float slot(float4 r) const { return c == 0 ? r.x : c == 1 ? r.y : c == 2 ? r.z : r.w; }
+    __device__ __forceinline__ float lo(int a) const { return slot(rows[a]); }
+    __device__ __forceinline__ float hi(int a) const { return slot(rows[3 + a]); }
+};
+struct ChildBox2 {
+    float lx, ly, lz, hx, hy, hz;
+    __device__ __forceinline__ float lo(int a) const { return pick3(lx, ly, lz, a); }
+    __device__ __forceinline__ float hi(int a) const { return pick3(hx, hy, hz, a); }
+    __device__ __forceinline__ float bound(int a, bool upper) const { return upper ? hi(a) : lo(a); }
+};
+
+// ---------------------------------------------------------------------------------------------
+// The tree walk of the point and box queries: closest point and nearest triangles on both trees (kOrdered), inside
+// and box overlap on a binary tree (unordered; bvh_inside_walk and bvh_box_walk say why their four-wide walks keep
+// loops of their own, which hold to the same invariants). One lane, one query, the tree from the root. The walk owns the loop, the stack, both node layouts and the leaf encoding;
+// a query brings
+//   bool child(box, float &key)   whether the child is wanted (box: ChildBox4 or ChildBox2); kOrdered: key is
+//                                 what the wanted children are ordered by, smallest first (not NaN)
+//   bool leaf(first, cnt)         the leaf's triangles, slots first .. first + cnt - 1 of leaf_idx / leaf_recs;
+//                                 true ends the walk
+// and its own tally of tests. Invariants:
+// * A wanted child (child() true, not an empty slot) is entered next or pushed, never both and never neither,
+//   and an unwanted one is neither: every leaf below wanted children only is met exactly once, so a count or a
+//   set of triangles comes out whatever the order.
+// * The order is therefore free where the result is a set or a count (kOrdered false: the lower wanted slot is
+//   entered and the other pushed). Nearest first (kOrdered:
+//   the nearest is entered, the others pushed far to near; four-wide by the five-exchange network when more
+//   than one is wanted) only saves work, for a child test whose bound tightens as leaves are met.
+// * A popped ref is not tested again: child() sees each box once, with the bound of that moment.
+// * visits counts inner nodes, once each.
+// * A leaf that ends the walk empties the stack, so the loop has one exit, and the nearest verdict's leaf
+//   (kNearAny) returns from inside its triangle loop rather than through a flag in the loop's condition: with a
+//   second exit or with the flag those kernels hold some twenty more scalar registers of lane masks and lose a
+//   wave of occupancy to them (profiles/shared_walk_kernel_resources.txt). The box verdict's leaf (kBoxAny) keeps
+//   the flag: there the other form costs two VGPRs more.
+// * The binary step decodes the child refs after the child tests. With the refs first the compiler issued the
+//   node's fourth load behind a wait for the first, and the binary closest-point kernels, same registers, ran
+//   4 to 7% slower on uniform points (profiles/shared_walk_bench_ab.txt); in this order they are the parent's
+//   instruction for instruction.
+// ---------------------------------------------------------------------------------------------
+template <int W, bool kOrdered, typename Child, typename Leaf>
+__device__ __forceinline__ void bvh_walk(const DevScene &sc, const LaneStack &stack, unsigned &visits, Child &&child, Leaf &&leaf) {
+    int sp = 0;
+    int32_t ref = 0;
+    while (true) {
+        if (ref >= 0) {
+            ++visits;
+            if constexpr (W == 4) {
+                static_assert(kOrdered, "the unordered four-wide walks keep loops of their own");
+                const float4 *np = reinterpret_cast<const float4 *>(sc.nodes4f + ref);
+                const float4 rows[6] = {np[0], np[1], np[2], np[3], np[4], np[5]};
+                const int4 ch = *reinterpret_cast<const int4 *>(np + 6);
+                int32_t rc[4] = {ch.x, ch.y, ch.z, ch.w};
+                float tc[4];   // a wanted child's key is finite; INFINITY marks the others (empty slots among them)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    float key = 0.0f;
+                    const bool want = child(ChildBox4{rows, k}, key) && rc[k] != kBvhEmpty;
+                    tc[k] = want ? fminf(key, FLT_MAX) : INFINITY;
+                }
+                const int nh = (tc[0] != INFINITY) + (tc[1] != INFINITY) + (tc[2] != INFINITY) + (tc[3] != INFINITY);
+                if (nh > 1) {
+                    cswap(tc[0], rc[0], tc[1], rc[1]);
+                    cswap(tc[2], rc[2], tc[3], rc[3]);
+                    cswap(tc[0], rc[0], tc[2], rc[2]);
+                    cswap(tc[1], rc[1], tc[3], rc[3]);
+                    cswap(tc[1], rc[1], tc[2], rc[2]);
+                } else {
+                    rc[0] = tc[0] != INFINITY ? rc[0] : tc[1] != INFINITY ? rc[1] : tc[2] != INFINITY ? rc[2] : rc[3];
+                }
+                if (nh > 3) stack.push(sp, rc[3]);   // far to near: the nearest of them ends on top
+                if (nh > 2) stack.push(sp, rc[2]);
+                if (nh > 1) stack.push(sp, rc[1]);
+                if (nh > 0) { ref = rc[0]; continue; }
+            } else {
+                const float4 *np = reinterpret_cast<const float4 *>(sc.nodes + ref);
+                const float4 q0 = np[0], q1 = np[1], q2 = np[2], q3 = np[3];
+                // BvhNode: lo0 = q0.xyz, hi0 = (q0.w, q1.x, q1.y), lo1 = (q1.z, q1.w, q2.x), hi1 = q2.yzw
+                float e0 = 0.0f, e1 = 0.0f;
+                const bool w0 = child(ChildBox2{q0.x, q0.y, q0.z, q0.w, q1.x, q1.y}, e0);
+                const bool w1 = child(ChildBox2{q1.z, q1.w, q2.x, q2.y, q2.z, q2.w}, e1);
+                const int32_t c0 = __float_as_int(q3.x), c1 = __float_as_int(q3.y);   // (decoded after the tests: the order the loads are issued in follows it)
+                const bool h0 = w0 && c0 != kBvhEmpty, h1 = w1 && c1 != kBvhEmpty;
+                if (h0 && h1) {
+                    const bool first0 = !kOrdered || e0 <= e1;
+                    stack.push(sp, first0 ? c1 : c0);
+                    ref = first0 ? c0 : c1;
+                    continue;
+                }
+                if (h0 || h1) { ref = h0 ? c0 : c1; continue; }
+            }
+        } else {
+            const uint32_t u = static_cast<uint32_t>(ref);
+            const int cnt = static_cast<int>((u >> kBvhCountShift) & kBvhCountMask);
+            const int first = static_cast<int>(u & ((1u << kBvhCountShift) - 1u));
+            if (leaf(first, cnt)) sp = 0;   // the walk ends where it always ends, below
+        }
+        if (sp == 0) break;
+        ref = stack.pop(sp);
+    }
+}
+
 // A four-wide node's rows for this ray (Bvh4F): the near and far bound rows of each axis (the
 // lower bounds are the near plane when the ray's direction component is positive, the upper bounds
 // when it is negative; Ray4::rows holds the byte offsets) and the child refs, as global loads from
@@ -498,19 +625,6 @@ __device__ __forceinline__ void bvh_query(const DevScene &sc, V3 o, V3 dir, bool
             ref = stack.pop(sp);
         }
     }
-}
-
-// Four-wide traversal (bvh.cpp, Bvh4F): the same cull and leaf logic as bvh_query; the hit
-// children are sorted by entry distance, the nearest is visited next and the others are pushed
-// farthest first.
-__device__ __forceinline__ void cswap(float &ta, int32_t &ra, float &tb, int32_t &rb) {
-    const bool sw = tb < ta;
-    const float t = sw ? tb : ta;
-    const int32_t r = sw ? rb : ra;
-    tb = sw ? ta : tb;
-    rb = sw ? ra : rb;
-    ta = t;
-    ra = r;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1476,6 +1590,16 @@ __device__ __forceinline__ int live_rays(const int32_t *__restrict__ d_count, in
     return d_count ? min(max(*d_count, 0), n) : n;
 }
 
+// The brute-force kernels' lane: query j (0 for an idle lane, which stays for the wave-wide steps and stores
+// nothing); false when the whole block lies past the live count.
+__device__ __forceinline__ bool brute_lane(const int32_t *__restrict__ d_count, int n, int &j, bool &active) {
+    const int live = live_rays(d_count, n);
+    const int64_t base = static_cast<int64_t>(blockIdx.x) * kBlock;
+    active = base + threadIdx.x < live;
+    j = active ? static_cast<int>(base + threadIdx.x) : 0;
+    return base < live;
+}
+
 template <int kMode>
 __device__ __forceinline__ void store_query(const uint32_t *__restrict__ tri_mat, const DevMaterial *__restrict__ mats, int j,
                                             int bidx, V3 bI, int32_t *__restrict__ idx, float *__restrict__ point,
@@ -1522,11 +1646,9 @@ __global__ __launch_bounds__(kBlock) void k_query_rays(const TriRec *__restrict_
                                                        const void *__restrict__ dst, int n, const int32_t *__restrict__ d_count,
                                                        int32_t *__restrict__ idx, float *__restrict__ point,
                                                        uint8_t *__restrict__ blocked) {
-    const int live = live_rays(d_count, n);
-    const int64_t base = static_cast<int64_t>(blockIdx.x) * kBlock;
-    if (base >= live) return;
-    const bool active = base + threadIdx.x < live;
-    const int j = active ? static_cast<int>(base + threadIdx.x) : 0;
+    int j;
+    bool active;
+    if (!brute_lane(d_count, n, j, active)) return;
     V3 o = mk(0, 0, 0), dir = mk(0, 0, 0);
     if (active) {
         o = load_ray_point<kStride>(org, j);
@@ -1652,11 +1774,9 @@ __global__ __launch_bounds__(kBlock) void k_range_rays(const TriRec *__restrict_
                                                        const DevMaterial *__restrict__ mats, const void *__restrict__ org,
                                                        const void *__restrict__ dst, int n, const int32_t *__restrict__ d_count,
                                                        const RangeQuery q) {
-    const int live = live_rays(d_count, n);
-    const int64_t base = static_cast<int64_t>(blockIdx.x) * kBlock;
-    if (base >= live) return;
-    const bool active = base + threadIdx.x < live;
-    const int j = active ? static_cast<int>(base + threadIdx.x) : 0;
+    int j;
+    bool active;
+    if (!brute_lane(d_count, n, j, active)) return;
     V3 o = mk(0, 0, 0), dir = mk(0, 0, 0);
     RayRange rg;
     rg.tri_mat = tri_mat;
@@ -1716,7 +1836,7 @@ __global__ __launch_bounds__(kBvhBlock) void k_bvh_multi_rays(const DevScene sc,
                                                               const int32_t *__restrict__ d_count, const MultiQuery q) {
     extern __shared__ int32_t lds_stack[];
     const LaneStack stack = lane_stack(sc, lds_stack);
-    unsigned long long *const lists = reinterpret_cast<unsigned long long *>(lds_stack + max(sc.lds_stack, 1) * kBvhBlock);
+    unsigned long long *const lists = reinterpret_cast<unsigned long long *>(lds_after_stack(sc, lds_stack));
     WorkTally<kCount> wt;
     drive_queries(live_rays(d_count, n), 0, nullptr, [&](int j, int end) {
         const bool active = j < end;
@@ -1751,11 +1871,9 @@ __global__ __launch_bounds__(kBlock) void k_multi_rays(const TriRec *__restrict_
                                                        const void *__restrict__ dst, int n, const int32_t *__restrict__ d_count,
                                                        const MultiQuery q) {
     extern __shared__ int32_t lds_stack[];   // the lists alone
-    const int live = live_rays(d_count, n);
-    const int64_t base = static_cast<int64_t>(blockIdx.x) * kBlock;
-    if (base >= live) return;
-    const bool active = base + threadIdx.x < live;
-    const int j = active ? static_cast<int>(base + threadIdx.x) : 0;
+    int j;
+    bool active;
+    if (!brute_lane(d_count, n, j, active)) return;
     V3 o = mk(0, 0, 0), dir = mk(0, 0, 0);
     RayRange rg;
     MultiList ml;
@@ -1886,10 +2004,16 @@ __device__ __forceinline__ float point_cull(float best2, float slack) {
     return (h * h) * 1.000001f;
 }
 
-__device__ __forceinline__ float box_dist2(V3 p, float lx, float ly, float lz, float hx, float hy, float hz) {
-    const float ex = fmaxf(fmaxf(lx - p.x, p.x - hx), 0.0f);
-    const float ey = fmaxf(fmaxf(ly - p.y, p.y - hy), 0.0f);
-    const float ez = fmaxf(fmaxf(lz - p.z, p.z - hz), 0.0f);
+__device__ __forceinline__ float point_slack(const DevScene &sc, V3 p) {
+    return 32.0f * 5.9604645e-08f * ((fabsf(p.x) + fabsf(p.y) + fabsf(p.z)) + sc.scene_m1);
+}
+
+// db2: the squared distance from p to a child's box (ChildBox4 / ChildBox2), bvh_walk's ordering key
+template <typename Box>
+__device__ __forceinline__ float box_dist2(V3 p, const Box &c) {
+    const float ex = fmaxf(fmaxf(c.lo(0) - p.x, p.x - c.hi(0)), 0.0f);
+    const float ey = fmaxf(fmaxf(c.lo(1) - p.y, p.y - c.hi(1)), 0.0f);
+    const float ez = fmaxf(fmaxf(c.lo(2) - p.z, p.z - c.hi(2)), 0.0f);
     return (ex * ex + ey * ey) + ez * ez;
 }
 
@@ -1900,68 +2024,22 @@ __device__ __forceinline__ void bvh_point_walk(const DevScene &sc, V3 p, bool wa
     for (int i = 0; i < sc.n_always; ++i) point_eval(sc.always_recs[i], static_cast<int>(sc.always[i]), p, best2, bidx);
     tests += static_cast<unsigned>(max(sc.n_always, 0));
     if (!walk) return;
-    const float slack = 32.0f * 5.9604645e-08f * ((fabsf(p.x) + fabsf(p.y) + fabsf(p.z)) + sc.scene_m1);
+    const float slack = point_slack(sc, p);
     float cull2 = point_cull(best2, slack);
-    int sp = 0;
-    int32_t ref = 0;
-    while (true) {
-        if (ref >= 0) {
-            ++visits;
-            if (W == 4) {
-                const float4 *np = reinterpret_cast<const float4 *>(sc.nodes4f + ref);
-                const float4 lx = np[0], ly = np[1], lz = np[2], hx = np[3], hy = np[4], hz = np[5];
-                const int4 ch = *reinterpret_cast<const int4 *>(np + 6);
-                int32_t rc[4] = {ch.x, ch.y, ch.z, ch.w};
-                const float blx[4] = {lx.x, lx.y, lx.z, lx.w}, bly[4] = {ly.x, ly.y, ly.z, ly.w}, blz[4] = {lz.x, lz.y, lz.z, lz.w};
-                const float bhx[4] = {hx.x, hx.y, hx.z, hx.w}, bhy[4] = {hy.x, hy.y, hy.z, hy.w}, bhz[4] = {hz.x, hz.y, hz.z, hz.w};
-                float tc[4];   // a wanted child's key is finite; INFINITY marks the others (empty slots among them)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float db2 = box_dist2(p, blx[k], bly[k], blz[k], bhx[k], bhy[k], bhz[k]);
-                    tc[k] = (db2 <= cull2 && rc[k] != kBvhEmpty) ? fminf(db2, FLT_MAX) : INFINITY;
-                }
-                const int nh = (tc[0] != INFINITY) + (tc[1] != INFINITY) + (tc[2] != INFINITY) + (tc[3] != INFINITY);
-                if (nh > 1) {
-                    cswap(tc[0], rc[0], tc[1], rc[1]);
-                    cswap(tc[2], rc[2], tc[3], rc[3]);
-                    cswap(tc[0], rc[0], tc[2], rc[2]);
-                    cswap(tc[1], rc[1], tc[3], rc[3]);
-                    cswap(tc[1], rc[1], tc[2], rc[2]);
-                } else {
-                    rc[0] = tc[0] != INFINITY ? rc[0] : tc[1] != INFINITY ? rc[1] : tc[2] != INFINITY ? rc[2] : rc[3];
-                }
-                if (nh > 3) stack.push(sp, rc[3]);   // far to near: the nearest of them ends on top
-                if (nh > 2) stack.push(sp, rc[2]);
-                if (nh > 1) stack.push(sp, rc[1]);
-                if (nh > 0) { ref = rc[0]; continue; }
-            } else {
-                const float4 *np = reinterpret_cast<const float4 *>(sc.nodes + ref);
-                const float4 q0 = np[0], q1 = np[1], q2 = np[2], q3 = np[3];
-                const float e0 = box_dist2(p, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y);
-                const float e1 = box_dist2(p, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w);
-                const int32_t c0 = __float_as_int(q3.x), c1 = __float_as_int(q3.y);
-                const bool h0 = e0 <= cull2 && c0 != kBvhEmpty, h1 = e1 <= cull2 && c1 != kBvhEmpty;
-                if (h0 && h1) {
-                    const bool first0 = e0 <= e1;
-                    stack.push(sp, first0 ? c1 : c0);
-                    ref = first0 ? c0 : c1;
-                    continue;
-                }
-                if (h0 || h1) { ref = h0 ? c0 : c1; continue; }
-            }
-        } else {
-            const uint32_t u = static_cast<uint32_t>(ref);
-            const int cnt = static_cast<int>((u >> kBvhCountShift) & kBvhCountMask);
-            const int first = static_cast<int>(u & ((1u << kBvhCountShift) - 1u));
+    bvh_walk<W, true>(
+        sc, stack, visits,
+        [&](const auto &c, float &db2) {
+            db2 = box_dist2(p, c);
+            return db2 <= cull2;
+        },
+        [&](int first, int cnt) {
             bool better = false;
             for (int k = 0; k < cnt; ++k)
                 better |= point_eval(leaf_rec(sc, first + k), static_cast<int>(sc.leaf_idx[first + k]), p, best2, bidx);
             tests += static_cast<unsigned>(cnt);
-            if (better) cull2 = point_cull(best2, slack);
-        }
-        if (sp == 0) break;
-        ref = stack.pop(sp);
-    }
+            if (better) cull2 = point_cull(best2, slack);   // (only when the bound fell: a node visit costs no sqrtf)
+            return false;
+        });
 }
 
 template <int W, int kStride, bool kCount>
@@ -1993,11 +2071,9 @@ __global__ __launch_bounds__(kBvhBlock) void k_bvh_point_query(const DevScene sc
 template <int kStride>
 __global__ __launch_bounds__(kBlock) void k_point_query(const TriRec *__restrict__ tris, int nt, const void *__restrict__ pts, int n,
                                                         const int32_t *__restrict__ d_count, const PointQuery q) {
-    const int live = live_rays(d_count, n);
-    const int64_t base = static_cast<int64_t>(blockIdx.x) * kBlock;
-    if (base >= live) return;
-    const bool active = base + threadIdx.x < live;
-    const int j = active ? static_cast<int>(base + threadIdx.x) : 0;
+    int j;
+    bool active;
+    if (!brute_lane(d_count, n, j, active)) return;
     V3 p = mk(0, 0, 0);
     float best2 = INFINITY;
     bool walk = false;
@@ -2025,8 +2101,8 @@ __global__ __launch_bounds__(kBlock) void k_point_query(const TriRec *__restrict
 // no margin (DESIGN.md §7 "Inside and signed-distance queries"): fl32(x - y) has the sign of x - y, a
 // triangle that covers the point has 0 within the ranges of its X_j and Y_j, one that is above has some
 // Z_j > 0, and every box of the tree contains its triangles' vertices. What is not skipped is evaluated with
-// the same arithmetic and the result is a count, so the visiting order does not matter: no sort, the first
-// wanted child is entered and the others pushed (at most three per four-wide node, one per binary node).
+// the same arithmetic and the result is a count, so the visiting order does not matter: bvh_walk's
+// unordered form (at most three pushes per four-wide node, one per binary node).
 // ---------------------------------------------------------------------------------------------
 struct InsideQuery {
     const float *xyz;           // the scene's vertices (3 per vertex) and
@@ -2036,8 +2112,6 @@ struct InsideQuery {
     int32_t *crossings;         // may be null
     int4 *hit;                  // may be null; else the records whose distance takes the sign
 };
-
-__device__ __forceinline__ float pick3(float x, float y, float z, int i) { return i == 0 ? x : i == 1 ? y : z; }
 
 // The direction's axes: k along it, (a, b) across, sg = +1 / -1.
 struct InsideAxes {
@@ -2094,57 +2168,55 @@ __device__ __forceinline__ int bvh_inside_walk(const DevScene &sc, const InsideQ
     if (!walk) return 0;
     const float pa = pick3(p.x, p.y, p.z, ax.a), pb = pick3(p.x, p.y, p.z, ax.b);
     const float spk = ax.sg * pick3(p.x, p.y, p.z, ax.k);   // (times +1 or -1: exact)
+    if constexpr (W == 2) {
+        bvh_walk<2, false>(
+            sc, stack, visits,
+            [&](const ChildBox2 &c, float &) {
+                // lo and hi across, and the bound the direction leaves through
+                const float la = c.lo(ax.a), ha = c.hi(ax.a), lb = c.lo(ax.b), hb = c.hi(ax.b), zk = c.bound(ax.k, ax.sg > 0.0f);
+                return !(pa < la || pa > ha || pb < lb || pb > hb || spk > ax.sg * zk);
+            },
+            [&](int first, int cnt) {
+                // the original index, then tri_v and xyz: the leaf-ordered records do not hold V1, V2
+                for (int k = 0; k < cnt; ++k) count += inside_eval(q, sc.tris, static_cast<int>(sc.leaf_idx[first + k]), p, ax);
+                tests += static_cast<unsigned>(cnt);
+                return false;
+            });
+        return count;
+    }
+    // Four-wide, the walk keeps a loop of its own (bvh_walk<4, false>'s, with another node step): the column needs
+    // five of a node's six rows, picked by an axis known only when the kernel runs, and bvh_walk's view cannot give
+    // that. A view that loaded the rows asked for measured 4 to 14% (rows pinned whole: k_bvh_inside<4, *, false> 48
+    // -> 63 / 64 VGPRs) or 25 to 40% slower (not pinned: a 4-byte load per slot and row) than this loop
+    // (profiles/shared_walk_bench_ab.txt, profiles/shared_walk_kernel_resources.txt); six rows would read one more.
     int sp = 0;
     int32_t ref = 0;
     while (true) {
         if (ref >= 0) {
             ++visits;
-            if (W == 4) {
-                const float4 *np = reinterpret_cast<const float4 *>(sc.nodes4f + ref);
-                // the rows the column needs: lo and hi across, and the bound the direction leaves through
-                const float4 la = np[ax.a], ha = np[3 + ax.a], lb = np[ax.b], hb = np[3 + ax.b];
-                const float4 zk = np[ax.sg > 0.0f ? 3 + ax.k : ax.k];
-                const int4 ch = *reinterpret_cast<const int4 *>(np + 6);
-                const int32_t rc[4] = {ch.x, ch.y, ch.z, ch.w};
-                const float cla[4] = {la.x, la.y, la.z, la.w}, cha[4] = {ha.x, ha.y, ha.z, ha.w};
-                const float clb[4] = {lb.x, lb.y, lb.z, lb.w}, chb[4] = {hb.x, hb.y, hb.z, hb.w};
-                const float czk[4] = {zk.x, zk.y, zk.z, zk.w};
-                int32_t next = kBvhEmpty;
+            const float4 *np = reinterpret_cast<const float4 *>(sc.nodes4f + ref);
+            // the rows the column needs: lo and hi across, and the bound the direction leaves through
+            const float4 la = np[ax.a], ha = np[3 + ax.a], lb = np[ax.b], hb = np[3 + ax.b];
+            const float4 zk = np[ax.sg > 0.0f ? 3 + ax.k : ax.k];
+            const int4 ch = *reinterpret_cast<const int4 *>(np + 6);
+            const int32_t rc[4] = {ch.x, ch.y, ch.z, ch.w};
+            const float cla[4] = {la.x, la.y, la.z, la.w}, cha[4] = {ha.x, ha.y, ha.z, ha.w};
+            const float clb[4] = {lb.x, lb.y, lb.z, lb.w}, chb[4] = {hb.x, hb.y, hb.z, hb.w};
+            const float czk[4] = {zk.x, zk.y, zk.z, zk.w};
+            int32_t next = kBvhEmpty;
 #pragma unroll
-                for (int c = 3; c >= 0; --c) {   // (the lowest wanted slot is entered, the others pushed)
-                    const bool skip = pa < cla[c] || pa > cha[c] || pb < clb[c] || pb > chb[c] || spk > ax.sg * czk[c];
-                    if (!skip && rc[c] != kBvhEmpty) {
-                        if (next != kBvhEmpty) stack.push(sp, next);
-                        next = rc[c];
-                    }
+            for (int c = 3; c >= 0; --c) {   // (the lowest wanted slot is entered, the others pushed)
+                const bool skip = pa < cla[c] || pa > cha[c] || pb < clb[c] || pb > chb[c] || spk > ax.sg * czk[c];
+                if (!skip && rc[c] != kBvhEmpty) {
+                    if (next != kBvhEmpty) stack.push(sp, next);
+                    next = rc[c];
                 }
-                if (next != kBvhEmpty) { ref = next; continue; }
-            } else {
-                const float4 *np = reinterpret_cast<const float4 *>(sc.nodes + ref);
-                const float4 q0 = np[0], q1 = np[1], q2 = np[2], q3 = np[3];
-                // BvhNode: lo0 = q0.xyz, hi0 = (q0.w, q1.x, q1.y), lo1 = (q1.z, q1.w, q2.x), hi1 = q2.yzw
-                const float l0a = pick3(q0.x, q0.y, q0.z, ax.a), h0a = pick3(q0.w, q1.x, q1.y, ax.a);
-                const float l0b = pick3(q0.x, q0.y, q0.z, ax.b), h0b = pick3(q0.w, q1.x, q1.y, ax.b);
-                const float l1a = pick3(q1.z, q1.w, q2.x, ax.a), h1a = pick3(q2.y, q2.z, q2.w, ax.a);
-                const float l1b = pick3(q1.z, q1.w, q2.x, ax.b), h1b = pick3(q2.y, q2.z, q2.w, ax.b);
-                const float z0 = ax.sg > 0.0f ? pick3(q0.w, q1.x, q1.y, ax.k) : pick3(q0.x, q0.y, q0.z, ax.k);
-                const float z1 = ax.sg > 0.0f ? pick3(q2.y, q2.z, q2.w, ax.k) : pick3(q1.z, q1.w, q2.x, ax.k);
-                const int32_t c0 = __float_as_int(q3.x), c1 = __float_as_int(q3.y);
-                const bool s0 = pa < l0a || pa > h0a || pb < l0b || pb > h0b || spk > ax.sg * z0;
-                const bool s1 = pa < l1a || pa > h1a || pb < l1b || pb > h1b || spk > ax.sg * z1;
-                const bool w0 = !s0 && c0 != kBvhEmpty, w1 = !s1 && c1 != kBvhEmpty;
-                if (w0 && w1) {
-                    stack.push(sp, c1);
-                    ref = c0;
-                    continue;
-                }
-                if (w0 || w1) { ref = w0 ? c0 : c1; continue; }
             }
+            if (next != kBvhEmpty) { ref = next; continue; }
         } else {
             const uint32_t u = static_cast<uint32_t>(ref);
             const int cnt = static_cast<int>((u >> kBvhCountShift) & kBvhCountMask);
             const int first = static_cast<int>(u & ((1u << kBvhCountShift) - 1u));
-            // the original index, then tri_v and xyz: the leaf-ordered records do not hold V1, V2
             for (int k = 0; k < cnt; ++k) count += inside_eval(q, sc.tris, static_cast<int>(sc.leaf_idx[first + k]), p, ax);
             tests += static_cast<unsigned>(cnt);
         }
@@ -2181,6 +2253,8 @@ __global__ __launch_bounds__(kBvhBlock) void k_bvh_inside(const DevScene sc, con
 template <int kStride>
 __global__ __launch_bounds__(kBlock) void k_inside(const TriRec *__restrict__ tris, int nt, const void *__restrict__ pts, int n,
                                                    const int32_t *__restrict__ d_count, const InsideQuery q) {
+    // (not brute_lane: no wave-wide step here, so an idle lane leaves at once; through brute_lane the loop measured
+    // 1.8% slower, profiles/shared_walk_bench_ab.txt)
     const int live = live_rays(d_count, n);
     const int64_t base = static_cast<int64_t>(blockIdx.x) * kBlock;
     if (base >= live) return;
@@ -2206,8 +2280,8 @@ __global__ __launch_bounds__(kBlock) void k_inside(const TriRec *__restrict__ tr
 // query box and the child's box are disjoint on some axis. That needs no margin (DESIGN.md §7 "Box-overlap
 // queries"): step 1 makes a triangle that overlaps have, on every axis, a vertex coordinate at or below hi and
 // one at or above lo, and every box of the tree contains its triangles' vertices. What is not skipped is
-// evaluated with the same arithmetic and the result is a set, so the visiting order does not matter: no sort,
-// the first wanted child is entered and the others pushed.
+// evaluated with the same arithmetic and the result is a set, so the visiting order does not matter:
+// bvh_walk's unordered form.
 // The list is BoxList: k ascending 32-bit indices per lane in dynamic LDS behind the traversal stack, laid out
 // as MultiList is ([slot][block lane]); an index needs no distance, so a slot is 4 bytes, not a 64-bit key. A
 // walk meets a triangle at most once, so no index comes twice. A triangle whose index is at or below `after`,
@@ -2337,44 +2411,52 @@ __device__ __forceinline__ void bvh_box_walk(const DevScene &sc, const BoxQuery 
         if (walk) box_visit<kMode>(q, sc.tris, static_cast<int>(sc.always[i]), b, after, bl, found);
     tests += static_cast<unsigned>(max(sc.n_always, 0));
     if (!walk || found) return;
+    if constexpr (W == 2) {
+        bvh_walk<2, false>(
+            sc, stack, visits,
+            [&](const ChildBox2 &c, float &) {
+                return !(b.lo.x > c.hx || b.hi.x < c.lx || b.lo.y > c.hy || b.hi.y < c.ly || b.lo.z > c.hz || b.hi.z < c.lz);
+            },
+            [&](int first, int cnt) {
+                // the original index, then tri_v and xyz: the leaf-ordered records do not hold V1, V2
+                if (kMode == kBoxAny) {
+                    for (int k = 0; k < cnt && !found; ++k) {
+                        box_visit<kMode>(q, sc.tris, static_cast<int>(sc.leaf_idx[first + k]), b, after, bl, found);
+                        ++tests;
+                    }
+                    return found;
+                }
+                for (int k = 0; k < cnt; ++k) box_visit<kMode>(q, sc.tris, static_cast<int>(sc.leaf_idx[first + k]), b, after, bl, found);
+                tests += static_cast<unsigned>(cnt);
+                return false;
+            });
+        return;
+    }
+    // Four-wide, the walk keeps a loop of its own, as bvh_inside_walk does: on bvh_walk, whose unordered four-wide step
+    // tested the four slots before it pushed any, the random-box legs measured 5 to 15% slower and the kernels held
+    // 2 to 6 VGPRs more (profiles/shared_walk_bench_ab.txt, profiles/shared_walk_kernel_resources.txt).
     int sp = 0;
     int32_t ref = 0;
     while (true) {
         if (ref >= 0) {
             ++visits;
-            if (W == 4) {
-                const float4 *np = reinterpret_cast<const float4 *>(sc.nodes4f + ref);
-                const float4 lx = np[0], ly = np[1], lz = np[2], hx = np[3], hy = np[4], hz = np[5];
-                const int4 ch = *reinterpret_cast<const int4 *>(np + 6);
-                const int32_t rc[4] = {ch.x, ch.y, ch.z, ch.w};
-                const float blx[4] = {lx.x, lx.y, lx.z, lx.w}, bly[4] = {ly.x, ly.y, ly.z, ly.w}, blz[4] = {lz.x, lz.y, lz.z, lz.w};
-                const float bhx[4] = {hx.x, hx.y, hx.z, hx.w}, bhy[4] = {hy.x, hy.y, hy.z, hy.w}, bhz[4] = {hz.x, hz.y, hz.z, hz.w};
-                int32_t next = kBvhEmpty;
+            const float4 *np = reinterpret_cast<const float4 *>(sc.nodes4f + ref);
+            const float4 lx = np[0], ly = np[1], lz = np[2], hx = np[3], hy = np[4], hz = np[5];
+            const int4 ch = *reinterpret_cast<const int4 *>(np + 6);
+            const int32_t rc[4] = {ch.x, ch.y, ch.z, ch.w};
+            const float blx[4] = {lx.x, lx.y, lx.z, lx.w}, bly[4] = {ly.x, ly.y, ly.z, ly.w}, blz[4] = {lz.x, lz.y, lz.z, lz.w};
+            const float bhx[4] = {hx.x, hx.y, hx.z, hx.w}, bhy[4] = {hy.x, hy.y, hy.z, hy.w}, bhz[4] = {hz.x, hz.y, hz.z, hz.w};
+            int32_t next = kBvhEmpty;
 #pragma unroll
-                for (int c = 3; c >= 0; --c) {   // (the lowest wanted slot is entered, the others pushed)
-                    const bool skip = b.lo.x > bhx[c] || b.hi.x < blx[c] || b.lo.y > bhy[c] || b.hi.y < bly[c] || b.lo.z > bhz[c] ||
-                                      b.hi.z < blz[c];
-                    if (!skip && rc[c] != kBvhEmpty) {
-                        if (next != kBvhEmpty) stack.push(sp, next);
-                        next = rc[c];
-                    }
+            for (int c = 3; c >= 0; --c) {   // (the lowest wanted slot is entered, the others pushed)
+                const bool skip = b.lo.x > bhx[c] || b.hi.x < blx[c] || b.lo.y > bhy[c] || b.hi.y < bly[c] || b.lo.z > bhz[c] ||
+                                  b.hi.z < blz[c];
+                if (!skip && rc[c] != kBvhEmpty) {
+                    if (next != kBvhEmpty) stack.push(sp, next);
+                    next = rc[c];
                 }
-                if (next != kBvhEmpty) { ref = next; continue; }
-            } else {
-                const float4 *np = reinterpret_cast<const float4 *>(sc.nodes + ref);
-                const float4 q0 = np[0], q1 = np[1], q2 = np[2], q3 = np[3];
-                // BvhNode: lo0 = q0.xyz, hi0 = (q0.w, q1.x, q1.y), lo1 = (q1.z, q1.w, q2.x), hi1 = q2.yzw
-                const bool s0 = b.lo.x > q0.w || b.hi.x < q0.x || b.lo.y > q1.x || b.hi.y < q0.y || b.lo.z > q1.y || b.hi.z < q0.z;
-                const bool s1 = b.lo.x > q2.y || b.hi.x < q1.z || b.lo.y > q2.z || b.hi.y < q1.w || b.lo.z > q2.w || b.hi.z < q2.x;
-                const int32_t c0 = __float_as_int(q3.x), c1 = __float_as_int(q3.y);
-                const bool w0 = !s0 && c0 != kBvhEmpty, w1 = !s1 && c1 != kBvhEmpty;
-                if (w0 && w1) {
-                    stack.push(sp, c1);
-                    ref = c0;
-                    continue;
-                }
-                if (w0 || w1) { ref = w0 ? c0 : c1; continue; }
             }
+            if (next != kBvhEmpty) { ref = next; continue; }
         } else {
             const uint32_t u = static_cast<uint32_t>(ref);
             const int cnt = static_cast<int>((u >> kBvhCountShift) & kBvhCountMask);
@@ -2421,7 +2503,7 @@ __global__ __launch_bounds__(kBvhBlock) void k_bvh_box(const DevScene sc, const 
                                                        const int32_t *__restrict__ d_count, const BoxQuery q) {
     extern __shared__ int32_t lds_stack[];
     const LaneStack stack = lane_stack(sc, lds_stack);
-    int32_t *const lists = lds_stack + max(sc.lds_stack, 1) * kBvhBlock;
+    int32_t *const lists = lds_after_stack(sc, lds_stack);
     WorkTally<kCount> wt;
     drive_queries(live_rays(d_count, n), 0, nullptr, [&](int j, int end) {
         const bool active = j < end;
@@ -2450,11 +2532,9 @@ template <int kStride, int kMode>
 __global__ __launch_bounds__(kBlock) void k_box(const TriRec *__restrict__ tris, int nt, const void *__restrict__ lo, int n,
                                                 const int32_t *__restrict__ d_count, const BoxQuery q) {
     extern __shared__ int32_t lds_stack[];   // the lists alone
-    const int live = live_rays(d_count, n);
-    const int64_t base = static_cast<int64_t>(blockIdx.x) * kBlock;
-    if (base >= live) return;
-    const bool active = base + threadIdx.x < live;
-    const int j = active ? static_cast<int>(base + threadIdx.x) : 0;
+    int j;
+    bool active;
+    if (!brute_lane(d_count, n, j, active)) return;
     QBox b;
     b.lo = b.hi = b.c = b.h = mk(0, 0, 0);
     int after = -1;
@@ -2499,7 +2579,6 @@ __global__ __launch_bounds__(kBlock) void k_box(const TriRec *__restrict__ tris,
 // recomputed only when kd changes: a node visit costs no sqrtf. kNearListAll never lowers best2, so it walks
 // the whole ball; kNearAny keeps no list, never lowers it either, and a lane leaves at its first candidate
 // below the bound (nearest child first, so usually soon).
-// The node step is bvh_point_walk's, repeated here so that the closest-point kernels compile as they did.
 // After the walk each kept triangle's record is recomputed from the scene's record (as store_point does) and
 // stored as one 16-byte row; rows past the list are the miss record. An empty search (load_point_bound) takes
 // no part in the walk: k miss rows, a count of 0, a verdict of 0.
@@ -2542,76 +2621,30 @@ __device__ __forceinline__ void bvh_point_walk_list(const DevScene &sc, V3 p, bo
     }
     tests += static_cast<unsigned>(max(sc.n_always, 0));
     if (!walk || found) return;
-    const float slack = 32.0f * 5.9604645e-08f * ((fabsf(p.x) + fabsf(p.y) + fabsf(p.z)) + sc.scene_m1);
+    const float slack = point_slack(sc, p);
     float cull2 = point_cull(best2, slack);
-    int sp = 0;
-    int32_t ref = 0;
-    while (true) {
-        if (ref >= 0) {
-            ++visits;
-            if (W == 4) {
-                const float4 *np = reinterpret_cast<const float4 *>(sc.nodes4f + ref);
-                const float4 lx = np[0], ly = np[1], lz = np[2], hx = np[3], hy = np[4], hz = np[5];
-                const int4 ch = *reinterpret_cast<const int4 *>(np + 6);
-                int32_t rc[4] = {ch.x, ch.y, ch.z, ch.w};
-                const float blx[4] = {lx.x, lx.y, lx.z, lx.w}, bly[4] = {ly.x, ly.y, ly.z, ly.w}, blz[4] = {lz.x, lz.y, lz.z, lz.w};
-                const float bhx[4] = {hx.x, hx.y, hx.z, hx.w}, bhy[4] = {hy.x, hy.y, hy.z, hy.w}, bhz[4] = {hz.x, hz.y, hz.z, hz.w};
-                float tc[4];   // a wanted child's key is finite; INFINITY marks the others (empty slots among them)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float db2 = box_dist2(p, blx[k], bly[k], blz[k], bhx[k], bhy[k], bhz[k]);
-                    tc[k] = (db2 <= cull2 && rc[k] != kBvhEmpty) ? fminf(db2, FLT_MAX) : INFINITY;
-                }
-                const int nh = (tc[0] != INFINITY) + (tc[1] != INFINITY) + (tc[2] != INFINITY) + (tc[3] != INFINITY);
-                if (nh > 1) {
-                    cswap(tc[0], rc[0], tc[1], rc[1]);
-                    cswap(tc[2], rc[2], tc[3], rc[3]);
-                    cswap(tc[0], rc[0], tc[2], rc[2]);
-                    cswap(tc[1], rc[1], tc[3], rc[3]);
-                    cswap(tc[1], rc[1], tc[2], rc[2]);
-                } else {
-                    rc[0] = tc[0] != INFINITY ? rc[0] : tc[1] != INFINITY ? rc[1] : tc[2] != INFINITY ? rc[2] : rc[3];
-                }
-                if (nh > 3) stack.push(sp, rc[3]);   // far to near: the nearest of them ends on top; each wanted
-                if (nh > 2) stack.push(sp, rc[2]);   // child is pushed or taken, never both, so no subtree is
-                if (nh > 1) stack.push(sp, rc[1]);   // walked twice (a count would notice)
-                if (nh > 0) { ref = rc[0]; continue; }
-            } else {
-                const float4 *np = reinterpret_cast<const float4 *>(sc.nodes + ref);
-                const float4 q0 = np[0], q1 = np[1], q2 = np[2], q3 = np[3];
-                const float e0 = box_dist2(p, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y);
-                const float e1 = box_dist2(p, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w);
-                const int32_t c0 = __float_as_int(q3.x), c1 = __float_as_int(q3.y);
-                const bool h0 = e0 <= cull2 && c0 != kBvhEmpty, h1 = e1 <= cull2 && c1 != kBvhEmpty;
-                if (h0 && h1) {
-                    const bool first0 = e0 <= e1;
-                    stack.push(sp, first0 ? c1 : c0);
-                    ref = first0 ? c0 : c1;
-                    continue;
-                }
-                if (h0 || h1) { ref = h0 ? c0 : c1; continue; }
-            }
-        } else {
-            const uint32_t u = static_cast<uint32_t>(ref);
-            const int cnt = static_cast<int>((u >> kBvhCountShift) & kBvhCountMask);
-            const int first = static_cast<int>(u & ((1u << kBvhCountShift) - 1u));
+    bvh_walk<W, true>(
+        sc, stack, visits,
+        [&](const auto &c, float &db2) {
+            db2 = box_dist2(p, c);
+            return db2 <= cull2;
+        },
+        [&](int first, int cnt) {
             if (kMode == kNearAny) {
-                for (int k = 0; k < cnt && !found; ++k) {
-                    near_eval<kMode>(leaf_rec(sc, first + k), static_cast<int>(sc.leaf_idx[first + k]), p, best2, bidx, ml, found);
+                for (int k = 0; k < cnt; ++k) {   // (found is false here: the first candidate ends the leaf and the walk)
                     ++tests;
+                    near_eval<kMode>(leaf_rec(sc, first + k), static_cast<int>(sc.leaf_idx[first + k]), p, best2, bidx, ml, found);
+                    if (found) return true;
                 }
-                if (found) return;
-            } else {
-                bool lower = false;
-                for (int k = 0; k < cnt; ++k)
-                    lower |= near_eval<kMode>(leaf_rec(sc, first + k), static_cast<int>(sc.leaf_idx[first + k]), p, best2, bidx, ml, found);
-                tests += static_cast<unsigned>(cnt);
-                if (lower) cull2 = point_cull(best2, slack);
+                return false;
             }
-        }
-        if (sp == 0) break;
-        ref = stack.pop(sp);
-    }
+            bool lower = false;
+            for (int k = 0; k < cnt; ++k)
+                lower |= near_eval<kMode>(leaf_rec(sc, first + k), static_cast<int>(sc.leaf_idx[first + k]), p, best2, bidx, ml, found);
+            tests += static_cast<unsigned>(cnt);
+            if (lower) cull2 = point_cull(best2, slack);   // (only when kd fell)
+            return false;
+        });
 }
 
 // The rows of one point: the list's keys in order, each triangle's record recomputed, then miss rows.
@@ -2638,7 +2671,7 @@ __global__ __launch_bounds__(kBvhBlock) void k_bvh_near_query(const DevScene sc,
                                                               const int32_t *__restrict__ d_count, const NearQuery q) {
     extern __shared__ int32_t lds_stack[];
     const LaneStack stack = lane_stack(sc, lds_stack);
-    unsigned long long *const lists = reinterpret_cast<unsigned long long *>(lds_stack + max(sc.lds_stack, 1) * kBvhBlock);
+    unsigned long long *const lists = reinterpret_cast<unsigned long long *>(lds_after_stack(sc, lds_stack));
     WorkTally<kCount> wt;
     drive_queries(live_rays(d_count, n), 0, nullptr, [&](int j, int end) {
         const bool active = j < end;
@@ -2674,11 +2707,9 @@ template <int kStride, bool kCountAll>
 __global__ __launch_bounds__(kBlock) void k_point_list_query(const TriRec *__restrict__ tris, int nt, const void *__restrict__ pts, int n,
                                                              const int32_t *__restrict__ d_count, const NearQuery q) {
     extern __shared__ int32_t lds_stack[];   // the lists alone
-    const int live = live_rays(d_count, n);
-    const int64_t base = static_cast<int64_t>(blockIdx.x) * kBlock;
-    if (base >= live) return;
-    const bool active = base + threadIdx.x < live;
-    const int j = active ? static_cast<int>(base + threadIdx.x) : 0;
+    int j;
+    bool active;
+    if (!brute_lane(d_count, n, j, active)) return;
     V3 p = mk(0, 0, 0);
     float best2 = INFINITY;
     bool walk = false;
@@ -2701,11 +2732,9 @@ __global__ __launch_bounds__(kBlock) void k_point_list_query(const TriRec *__res
 template <int kStride>
 __global__ __launch_bounds__(kBlock) void k_point_any_query(const TriRec *__restrict__ tris, int nt, const void *__restrict__ pts, int n,
                                                             const int32_t *__restrict__ d_count, const NearQuery q) {
-    const int live = live_rays(d_count, n);
-    const int64_t base = static_cast<int64_t>(blockIdx.x) * kBlock;
-    if (base >= live) return;
-    const bool active = base + threadIdx.x < live;
-    const int j = active ? static_cast<int>(base + threadIdx.x) : 0;
+    int j;
+    bool active;
+    if (!brute_lane(d_count, n, j, active)) return;
     V3 p = mk(0, 0, 0);
     float best2 = INFINITY;
     bool walk = false;
@@ -5089,9 +5118,9 @@ void launch_gen_rays(const float4 *org, const float4 *dst, int32_t n, const DevW
 inline size_t bvh_lds(const DevScene &s, int lanes = kBvhBlock) {
     return sizeof(int32_t) * lanes * static_cast<size_t>(std::max(s.lds_stack, 1));
 }
-// LDS of the multi-hit kernels' lists: k 64-bit keys per lane
-inline size_t multi_lds(int k, int lanes) { return sizeof(unsigned long long) * lanes * static_cast<size_t>(k); }
-inline DevScene for_width(DevScene s, int) { return s; }
+// LDS per lane of the lists behind the stack: k 64-bit keys (multi-hit, nearest triangles), k 32-bit indices (box overlap)
+inline size_t multi_lds(int k) { return sizeof(unsigned long long) * static_cast<size_t>(k); }
+inline size_t box_lds(int k) { return sizeof(int32_t) * static_cast<size_t>(k); }
 
 // Grid cap of the per-step BVH kernels (resident size at 7 waves per SIMD: a grid-stride walk).
 constexpr int kMaxBvhGrid = 4096;
@@ -5103,8 +5132,7 @@ inline unsigned grid_chunked(int64_t n) {
 }
 
 template <int W>
-void launch_ch(const DevScene &s0, const DevWork &w, int step, int64_t capacity, hipStream_t stream) {
-    const DevScene s = for_width(s0, W);
+void launch_ch(const DevScene &s, const DevWork &w, int step, int64_t capacity, hipStream_t stream) {
     auto k = s.work ? k_bvh_closest_hit<W, true> : k_bvh_closest_hit<W, false>;
     hipLaunchKernelGGL(k, dim3(grid_bvh(capacity, s.bvh_grid)), dim3(kBvhBlock), bvh_lds(s), stream, s,
                        w.q_org[step & 1], w.q_dst[step & 1], &w.counters[step], w.hit_idx, w.hit_I,
@@ -5134,9 +5162,8 @@ void launch_shadow_gen(const DevScene &, const DevWork &w, const ShadeParams &p,
 }
 
 template <int W>
-void launch_sh(const DevScene &s0, const DevWork &w, const ShadowSource &src, int step, int64_t capacity,
+void launch_sh(const DevScene &s, const DevWork &w, const ShadowSource &src, int step, int64_t capacity,
                hipStream_t stream) {
-    const DevScene s = for_width(s0, W);
     auto k = s.any_transparent ? k_bvh_shadow_hit<false, W, false> : k_bvh_shadow_hit<true, W, false>;
     if (s.work) k = s.any_transparent ? k_bvh_shadow_hit<false, W, true> : k_bvh_shadow_hit<true, W, true>;
     hipLaunchKernelGGL(k, dim3(grid_bvh(capacity, s.bvh_grid)), dim3(kBvhBlock), bvh_lds(s), stream, s, src, w.shadow,
@@ -5248,12 +5275,11 @@ hipError_t probe_chain_kernargs(hipStream_t stream, uint32_t *bad, int *which) {
     return ef;
 }
 
-void launch_chain(const DevScene &s0, const DevWork &w, const ShadeParams &p, int first, int64_t capacity,
+void launch_chain(const DevScene &s, const DevWork &w, const ShadeParams &p, int first, int64_t capacity,
                   hipStream_t stream, bool ordered, uint8_t *out_u8, float *out_f32, int fuse_spp, const FrameGeom *g,
                   const FrameSet *fs) {
     if (capacity <= 0) return;
-    const bool wide = s0.bvh_width == 4;
-    const DevScene s = for_width(s0, wide ? 4 : 2);
+    const bool wide = s.bvh_width == 4;
     const bool anyhit = !s.any_transparent, count = s.work != nullptr;
     // fused pixel writes from step 0: each lane makes its primary ray and folds its own chain
     const bool fused = fuse_spp > 0 && fuse_spp <= kWave && first == 0 && g != nullptr;
@@ -5298,17 +5324,16 @@ void launch_chain(const DevScene &s0, const DevWork &w, const ShadeParams &p, in
                        geom, split, s8, frames);
 }
 
-void launch_estimate(const DevScene &s0, const ShadeParams &p, const FrameGeom &g, int fuse_spp, int64_t capacity,
+void launch_estimate(const DevScene &s, const ShadeParams &p, const FrameGeom &g, int fuse_spp, int64_t capacity,
                      uint32_t *score, hipStream_t stream) {
     const int64_t nbatch = chain_batches(capacity, fuse_spp);
     if (nbatch <= 0) return;
-    if (s0.cold_estimate == 2) {
+    if (s.cold_estimate == 2) {
         hipLaunchKernelGGL(k_estimate_center, dim3(grid_for(nbatch)), dim3(kBlock), 0, stream, with_divisors(g),
                            chain_spb(fuse_spp), static_cast<int>(nbatch), score);
         return;
     }
-    const bool wide = s0.bvh_width == 4;
-    const DevScene s = for_width(s0, wide ? 4 : 2);
+    const bool wide = s.bvh_width == 4;
     const unsigned grid = static_cast<unsigned>((nbatch + kBvhBlock - 1) / kBvhBlock);
     hipLaunchKernelGGL(wide ? k_estimate<4> : k_estimate<2>, dim3(grid), dim3(kBvhBlock), bvh_lds(s), stream, s, p,
                        with_divisors(g), chain_spb(fuse_spp), static_cast<int>(nbatch), score);
@@ -5397,75 +5422,71 @@ void launch_fold_rays(const DevWork &w, int32_t n, float *rgb, hipStream_t strea
     hipLaunchKernelGGL(k_fold_rays, dim3(grid_for(n)), dim3(kBlock), 0, stream, w, n, rgb);
 }
 
-void launch_intersect_only(const DevScene &s0, const float4 *org, const float4 *dst, int32_t n, int32_t *idx,
-                           float4 *I, hipStream_t stream) {
-    if (n <= 0) return;
-    if (s0.use_bvh) {
-        const int W = s0.bvh_width == 4 ? 4 : 2;
-        const DevScene s = for_width(s0, W);
-        auto k = W == 4 ? (s.work ? k_bvh_intersect_only<4, true> : k_bvh_intersect_only<4, false>)
-                        : (s.work ? k_bvh_intersect_only<2, true> : k_bvh_intersect_only<2, false>);
-        hipLaunchKernelGGL(k, dim3(grid_bvh(n, s.bvh_grid)), dim3(kBvhBlock), bvh_lds(s), stream, s, org, dst, n, idx, I);
-        return;
+namespace {
+// The launch of every query kernel. On a tree: the kernel that bvh(W, kCount) names for the tree's width and for
+// counting work or not (two std::integral_constants in, a kernel out: one pointer type for the four), as a
+// grid-stride walk with the stack's LDS and lane_lds more bytes per lane (the list kernels' lists), on
+// (s, args...). Without one: `brute`, one lane per query with lane_lds per lane, on (s.tris, s.nt, args...), or
+// (kMaterials: the ray queries whose loops read the hit's material) on (s.tris, s.nt, s.tri_mat, s.mats, args...).
+template <int V>
+using Int = std::integral_constant<int, V>;
+template <bool kMaterials = false, typename Bvh, typename Brute, typename... Args>
+void launch_query(const DevScene &s, int32_t n, size_t lane_lds, hipStream_t stream, Bvh bvh, Brute brute, Args... args) {
+    if (s.use_bvh) {
+        auto k = s.bvh_width == 4 ? (s.work ? bvh(Int<4>{}, std::true_type{}) : bvh(Int<4>{}, std::false_type{}))
+                                  : (s.work ? bvh(Int<2>{}, std::true_type{}) : bvh(Int<2>{}, std::false_type{}));
+        hipLaunchKernelGGL(k, dim3(grid_bvh(n, s.bvh_grid)), dim3(kBvhBlock), bvh_lds(s) + lane_lds * kBvhBlock, stream, s, args...);
+    } else if constexpr (kMaterials) {
+        hipLaunchKernelGGL(brute, dim3(grid_for(n)), dim3(kBlock), lane_lds * kBlock, stream, s.tris, s.nt, s.tri_mat, s.mats, args...);
+    } else {
+        hipLaunchKernelGGL(brute, dim3(grid_for(n)), dim3(kBlock), lane_lds * kBlock, stream, s.tris, s.nt, args...);
     }
-    hipLaunchKernelGGL(k_intersect_only, dim3(grid_for(n)), dim3(kBlock), 0, stream, s0.tris, s0.nt, org, dst, n, idx, I);
+}
+
+// f(Int<4>) for one float4 per ray, point or corner, f(Int<3>) for three packed floats.
+template <typename F>
+void for_stride(int32_t stride, F &&f) {
+    if (stride == 4) f(Int<4>{});
+    else f(Int<3>{});
+}
+}  // namespace
+
+void launch_intersect_only(const DevScene &s, const float4 *org, const float4 *dst, int32_t n, int32_t *idx, float4 *I,
+                           hipStream_t stream) {
+    if (n <= 0) return;
+    launch_query(s, n, 0, stream, [](auto w, auto c) { return k_bvh_intersect_only<w, c>; }, k_intersect_only, org, dst, n, idx, I);
 }
 
 namespace {
-template <int kMode, int kStride>
-void launch_query_mode(const DevScene &s0, const void *org, const void *dst, int32_t n, const int32_t *d_count, int32_t *idx,
-                       float *point, uint8_t *blocked, hipStream_t stream) {
-    if (s0.use_bvh) {   // launch_intersect_only's shape
-        const int W = s0.bvh_width == 4 ? 4 : 2;
-        const DevScene s = for_width(s0, W);
-        auto k = W == 4 ? (s.work ? k_bvh_query_rays<4, kMode, kStride, true> : k_bvh_query_rays<4, kMode, kStride, false>)
-                        : (s.work ? k_bvh_query_rays<2, kMode, kStride, true> : k_bvh_query_rays<2, kMode, kStride, false>);
-        hipLaunchKernelGGL(k, dim3(grid_bvh(n, s.bvh_grid)), dim3(kBvhBlock), bvh_lds(s), stream, s, org, dst, n, d_count, idx,
-                           point, blocked);
-        return;
-    }
-    hipLaunchKernelGGL((k_query_rays<kMode, kStride>), dim3(grid_for(n)), dim3(kBlock), 0, stream, s0.tris, s0.nt, s0.tri_mat,
-                       s0.mats, org, dst, n, d_count, idx, point, blocked);
+template <int kMode>
+void launch_query_mode(const DevScene &s, const void *org, const void *dst, int32_t ray_stride, int32_t n, const int32_t *d_count,
+                       int32_t *idx, float *point, uint8_t *blocked, hipStream_t stream) {
+    for_stride(ray_stride, [&](auto st) {
+        constexpr int kStride = st;
+        launch_query<true>(s, n, 0, stream, [](auto w, auto c) { return k_bvh_query_rays<w, kMode, kStride, c>; },
+                     k_query_rays<kMode, kStride>, org, dst, n, d_count, idx, point, blocked);
+    });
 }
 }  // namespace
 
 void launch_query_rays(const DevScene &s, bool occluded, const void *org, const void *dst, int32_t ray_stride, int32_t n,
                        const int32_t *d_count, int32_t *idx, float *point, uint8_t *blocked, hipStream_t stream) {
     if (n <= 0) return;
-    const bool wide = ray_stride == 4;
-    if (!occluded) {
-        if (wide) launch_query_mode<kQueryClosest, 4>(s, org, dst, n, d_count, idx, point, blocked, stream);
-        else launch_query_mode<kQueryClosest, 3>(s, org, dst, n, d_count, idx, point, blocked, stream);
-    } else if (s.any_transparent) {   // a transparent closest hit does not block, whatever lies behind it
-        if (wide) launch_query_mode<kQueryOccludedClosest, 4>(s, org, dst, n, d_count, idx, point, blocked, stream);
-        else launch_query_mode<kQueryOccludedClosest, 3>(s, org, dst, n, d_count, idx, point, blocked, stream);
-    } else {
-        if (wide) launch_query_mode<kQueryOccludedAny, 4>(s, org, dst, n, d_count, idx, point, blocked, stream);
-        else launch_query_mode<kQueryOccludedAny, 3>(s, org, dst, n, d_count, idx, point, blocked, stream);
-    }
+    if (!occluded) launch_query_mode<kQueryClosest>(s, org, dst, ray_stride, n, d_count, idx, point, blocked, stream);
+    else if (s.any_transparent)   // a transparent closest hit does not block, whatever lies behind it
+        launch_query_mode<kQueryOccludedClosest>(s, org, dst, ray_stride, n, d_count, idx, point, blocked, stream);
+    else launch_query_mode<kQueryOccludedAny>(s, org, dst, ray_stride, n, d_count, idx, point, blocked, stream);
 }
 
 namespace {
-template <int kMode, int kStride>
-void launch_range_mode(const DevScene &s0, const void *org, const void *dst, int32_t n, const int32_t *d_count, const RangeQuery &q,
-                       hipStream_t stream) {
-    if (s0.use_bvh) {   // launch_query_mode's shape
-        const int W = s0.bvh_width == 4 ? 4 : 2;
-        const DevScene s = for_width(s0, W);
-        auto k = W == 4 ? (s.work ? k_bvh_range_rays<4, kMode, kStride, true> : k_bvh_range_rays<4, kMode, kStride, false>)
-                        : (s.work ? k_bvh_range_rays<2, kMode, kStride, true> : k_bvh_range_rays<2, kMode, kStride, false>);
-        hipLaunchKernelGGL(k, dim3(grid_bvh(n, s.bvh_grid)), dim3(kBvhBlock), bvh_lds(s), stream, s, org, dst, n, d_count, q);
-        return;
-    }
-    hipLaunchKernelGGL((k_range_rays<kMode, kStride>), dim3(grid_for(n)), dim3(kBlock), 0, stream, s0.tris, s0.nt, s0.tri_mat,
-                       s0.mats, org, dst, n, d_count, q);
-}
-
 template <int kMode>
-void launch_range_stride(const DevScene &s, const void *org, const void *dst, int32_t ray_stride, int32_t n, const int32_t *d_count,
-                         const RangeQuery &q, hipStream_t stream) {
-    if (ray_stride == 4) launch_range_mode<kMode, 4>(s, org, dst, n, d_count, q, stream);
-    else launch_range_mode<kMode, 3>(s, org, dst, n, d_count, q, stream);
+void launch_range_mode(const DevScene &s, const void *org, const void *dst, int32_t ray_stride, int32_t n, const int32_t *d_count,
+                       const RangeQuery &q, hipStream_t stream) {
+    for_stride(ray_stride, [&](auto st) {
+        constexpr int kStride = st;
+        launch_query<true>(s, n, 0, stream, [](auto w, auto c) { return k_bvh_range_rays<w, kMode, kStride, c>; },
+                     k_range_rays<kMode, kStride>, org, dst, n, d_count, q);
+    });
 }
 }  // namespace
 
@@ -5474,27 +5495,21 @@ void launch_range_rays(const DevScene &s, bool occluded, bool any_opaque, bool t
                        float *point, uint8_t *blocked, hipStream_t stream) {
     if (n <= 0) return;
     const RangeQuery q{d_tmin, d_tmax, to_dest ? 1 : 0, static_cast<int4 *>(hit), point, blocked};
-    if (!occluded) launch_range_stride<kRangeClosest>(s, org, dst, ray_stride, n, d_count, q, stream);
-    else if (!s.any_transparent) launch_range_stride<kRangeOccludedAny>(s, org, dst, ray_stride, n, d_count, q, stream);   // either rule
-    else if (any_opaque) launch_range_stride<kRangeOccludedAnyOpaque>(s, org, dst, ray_stride, n, d_count, q, stream);
-    else launch_range_stride<kRangeOccludedClosest>(s, org, dst, ray_stride, n, d_count, q, stream);
+    if (!occluded) launch_range_mode<kRangeClosest>(s, org, dst, ray_stride, n, d_count, q, stream);
+    else if (!s.any_transparent) launch_range_mode<kRangeOccludedAny>(s, org, dst, ray_stride, n, d_count, q, stream);   // either rule
+    else if (any_opaque) launch_range_mode<kRangeOccludedAnyOpaque>(s, org, dst, ray_stride, n, d_count, q, stream);
+    else launch_range_mode<kRangeOccludedClosest>(s, org, dst, ray_stride, n, d_count, q, stream);
 }
 
 namespace {
-template <int kStride, bool kCountAll>
-void launch_multi_mode(const DevScene &s0, const void *org, const void *dst, int32_t n, const int32_t *d_count, const MultiQuery &q,
-                       hipStream_t stream) {
-    if (s0.use_bvh) {   // launch_range_mode's shape; the lists' LDS follows the stack's
-        const int W = s0.bvh_width == 4 ? 4 : 2;
-        const DevScene s = for_width(s0, W);
-        auto k = W == 4 ? (s.work ? k_bvh_multi_rays<4, kStride, true, kCountAll> : k_bvh_multi_rays<4, kStride, false, kCountAll>)
-                        : (s.work ? k_bvh_multi_rays<2, kStride, true, kCountAll> : k_bvh_multi_rays<2, kStride, false, kCountAll>);
-        hipLaunchKernelGGL(k, dim3(grid_bvh(n, s.bvh_grid)), dim3(kBvhBlock), bvh_lds(s) + multi_lds(q.k, kBvhBlock), stream, s, org, dst,
-                           n, d_count, q);
-        return;
-    }
-    hipLaunchKernelGGL((k_multi_rays<kStride, kCountAll>), dim3(grid_for(n)), dim3(kBlock), multi_lds(q.k, kBlock), stream, s0.tris,
-                       s0.nt, org, dst, n, d_count, q);
+template <bool kCountAll>
+void launch_multi_mode(const DevScene &s, const void *org, const void *dst, int32_t ray_stride, int32_t n, const int32_t *d_count,
+                       const MultiQuery &q, hipStream_t stream) {
+    for_stride(ray_stride, [&](auto st) {
+        constexpr int kStride = st;
+        launch_query(s, n, multi_lds(q.k), stream, [](auto w, auto c) { return k_bvh_multi_rays<w, kStride, c, kCountAll>; },
+                     k_multi_rays<kStride, kCountAll>, org, dst, n, d_count, q);
+    });
 }
 }  // namespace
 
@@ -5503,85 +5518,40 @@ void launch_multi_rays(const DevScene &s, bool count_all, bool to_dest, const vo
                        int32_t *nhits, hipStream_t stream) {
     if (n <= 0) return;
     const MultiQuery q{d_tmin, d_tmax, to_dest ? 1 : 0, k, static_cast<int4 *>(hits), nhits};
-    const bool wide = ray_stride == 4;
-    if (count_all) {
-        if (wide) launch_multi_mode<4, true>(s, org, dst, n, d_count, q, stream);
-        else launch_multi_mode<3, true>(s, org, dst, n, d_count, q, stream);
-    } else {
-        if (wide) launch_multi_mode<4, false>(s, org, dst, n, d_count, q, stream);
-        else launch_multi_mode<3, false>(s, org, dst, n, d_count, q, stream);
-    }
+    if (count_all) launch_multi_mode<true>(s, org, dst, ray_stride, n, d_count, q, stream);
+    else launch_multi_mode<false>(s, org, dst, ray_stride, n, d_count, q, stream);
 }
-
-namespace {
-template <int kStride>
-void launch_point_mode(const DevScene &s0, const void *pts, int32_t n, const int32_t *d_count, const PointQuery &q, hipStream_t stream) {
-    if (s0.use_bvh) {   // launch_range_mode's shape
-        const int W = s0.bvh_width == 4 ? 4 : 2;
-        const DevScene s = for_width(s0, W);
-        auto k = W == 4 ? (s.work ? k_bvh_point_query<4, kStride, true> : k_bvh_point_query<4, kStride, false>)
-                        : (s.work ? k_bvh_point_query<2, kStride, true> : k_bvh_point_query<2, kStride, false>);
-        hipLaunchKernelGGL(k, dim3(grid_bvh(n, s.bvh_grid)), dim3(kBvhBlock), bvh_lds(s), stream, s, pts, n, d_count, q);
-        return;
-    }
-    hipLaunchKernelGGL((k_point_query<kStride>), dim3(grid_for(n)), dim3(kBlock), 0, stream, s0.tris, s0.nt, pts, n, d_count, q);
-}
-}  // namespace
 
 void launch_point_query(const DevScene &s, const void *pts, int32_t point_stride, int32_t n, const int32_t *d_count,
                         const float *d_rmax, void *hit, float *point, hipStream_t stream) {
     if (n <= 0) return;
     const PointQuery q{d_rmax, static_cast<int4 *>(hit), point};
-    if (point_stride == 4) launch_point_mode<4>(s, pts, n, d_count, q, stream);
-    else launch_point_mode<3>(s, pts, n, d_count, q, stream);
+    for_stride(point_stride, [&](auto st) {
+        constexpr int kStride = st;
+        launch_query(s, n, 0, stream, [](auto w, auto c) { return k_bvh_point_query<w, kStride, c>; }, k_point_query<kStride>, pts, n,
+                     d_count, q);
+    });
 }
-
-namespace {
-template <int kStride>
-void launch_inside_mode(const DevScene &s0, const void *pts, int32_t n, const int32_t *d_count, const InsideQuery &q, hipStream_t stream) {
-    if (s0.use_bvh) {   // launch_point_mode's shape
-        const int W = s0.bvh_width == 4 ? 4 : 2;
-        const DevScene s = for_width(s0, W);
-        auto k = W == 4 ? (s.work ? k_bvh_inside<4, kStride, true> : k_bvh_inside<4, kStride, false>)
-                        : (s.work ? k_bvh_inside<2, kStride, true> : k_bvh_inside<2, kStride, false>);
-        hipLaunchKernelGGL(k, dim3(grid_bvh(n, s.bvh_grid)), dim3(kBvhBlock), bvh_lds(s), stream, s, pts, n, d_count, q);
-        return;
-    }
-    hipLaunchKernelGGL((k_inside<kStride>), dim3(grid_for(n)), dim3(kBlock), 0, stream, s0.tris, s0.nt, pts, n, d_count, q);
-}
-}  // namespace
 
 void launch_inside_query(const DevScene &s, const float *xyz, const uint32_t *tri_v, const void *pts, int32_t point_stride, int32_t n,
                          const int32_t *d_count, int32_t axis, uint8_t *inside, int32_t *crossings, void *hit, hipStream_t stream) {
     if (n <= 0) return;
     const InsideQuery q{xyz, tri_v, axis, inside, crossings, static_cast<int4 *>(hit)};
-    if (point_stride == 4) launch_inside_mode<4>(s, pts, n, d_count, q, stream);
-    else launch_inside_mode<3>(s, pts, n, d_count, q, stream);
+    for_stride(point_stride, [&](auto st) {
+        constexpr int kStride = st;
+        launch_query(s, n, 0, stream, [](auto w, auto c) { return k_bvh_inside<w, kStride, c>; }, k_inside<kStride>, pts, n, d_count, q);
+    });
 }
 
 namespace {
-// LDS of the box kernels' lists: k 32-bit indices per lane
-inline size_t box_lds(int k, int lanes) { return sizeof(int32_t) * lanes * static_cast<size_t>(k); }
-template <int kStride, int kMode>
-void launch_box_mode(const DevScene &s0, const void *lo, int32_t n, const int32_t *d_count, const BoxQuery &q, hipStream_t stream) {
-    constexpr bool kList = kMode != kBoxAny;
-    if (s0.use_bvh) {   // launch_near_mode's shape; the lists' LDS follows the stack's
-        const int W = s0.bvh_width == 4 ? 4 : 2;
-        const DevScene s = for_width(s0, W);
-        auto k = W == 4 ? (s.work ? k_bvh_box<4, kStride, kMode, true> : k_bvh_box<4, kStride, kMode, false>)
-                        : (s.work ? k_bvh_box<2, kStride, kMode, true> : k_bvh_box<2, kStride, kMode, false>);
-        hipLaunchKernelGGL(k, dim3(grid_bvh(n, s.bvh_grid)), dim3(kBvhBlock), bvh_lds(s) + (kList ? box_lds(q.k, kBvhBlock) : 0), stream, s,
-                           lo, n, d_count, q);
-        return;
-    }
-    hipLaunchKernelGGL((k_box<kStride, kMode>), dim3(grid_for(n)), dim3(kBlock), kList ? box_lds(q.k, kBlock) : 0, stream, s0.tris, s0.nt,
-                       lo, n, d_count, q);
-}
 template <int kMode>
-void launch_box_stride(const DevScene &s, const void *lo, int32_t box_stride, int32_t n, const int32_t *d_count, const BoxQuery &q,
-                       hipStream_t stream) {
-    if (box_stride == 4) launch_box_mode<4, kMode>(s, lo, n, d_count, q, stream);
-    else launch_box_mode<3, kMode>(s, lo, n, d_count, q, stream);
+void launch_box_mode(const DevScene &s, const void *lo, int32_t box_stride, int32_t n, const int32_t *d_count, const BoxQuery &q,
+                     hipStream_t stream) {
+    for_stride(box_stride, [&](auto st) {
+        constexpr int kStride = st;
+        launch_query(s, n, kMode != kBoxAny ? box_lds(q.k) : 0, stream, [](auto w, auto c) { return k_bvh_box<w, kStride, kMode, c>; },
+                     k_box<kStride, kMode>, lo, n, d_count, q);
+    });
 }
 }  // namespace
 
@@ -5590,41 +5560,27 @@ void launch_box_query(const DevScene &s, const float *xyz, const uint32_t *tri_v
                       int32_t *nfound, hipStream_t stream) {
     if (n <= 0) return;
     const BoxQuery q{xyz, tri_v, hi, after, k, tris_out, nfound, nullptr};
-    if (count_all) launch_box_stride<kBoxListAll>(s, lo, box_stride, n, d_count, q, stream);
-    else launch_box_stride<kBoxList>(s, lo, box_stride, n, d_count, q, stream);
+    if (count_all) launch_box_mode<kBoxListAll>(s, lo, box_stride, n, d_count, q, stream);
+    else launch_box_mode<kBoxList>(s, lo, box_stride, n, d_count, q, stream);
 }
 
 void launch_box_occupied(const DevScene &s, const float *xyz, const uint32_t *tri_v, const void *lo, const void *hi, int32_t box_stride,
                          int32_t n, const int32_t *d_count, uint8_t *occupied, hipStream_t stream) {
     if (n <= 0) return;
     const BoxQuery q{xyz, tri_v, hi, nullptr, 0, nullptr, nullptr, occupied};
-    launch_box_stride<kBoxAny>(s, lo, box_stride, n, d_count, q, stream);
+    launch_box_mode<kBoxAny>(s, lo, box_stride, n, d_count, q, stream);
 }
 
 namespace {
-template <int kStride, int kMode>
-void launch_near_mode(const DevScene &s0, const void *pts, int32_t n, const int32_t *d_count, const NearQuery &q, hipStream_t stream) {
-    constexpr bool kList = kMode != kNearAny;
-    if (s0.use_bvh) {   // launch_multi_mode's shape; the lists' LDS follows the stack's
-        const int W = s0.bvh_width == 4 ? 4 : 2;
-        const DevScene s = for_width(s0, W);
-        auto k = W == 4 ? (s.work ? k_bvh_near_query<4, kStride, true, kMode> : k_bvh_near_query<4, kStride, false, kMode>)
-                        : (s.work ? k_bvh_near_query<2, kStride, true, kMode> : k_bvh_near_query<2, kStride, false, kMode>);
-        hipLaunchKernelGGL(k, dim3(grid_bvh(n, s.bvh_grid)), dim3(kBvhBlock), bvh_lds(s) + (kList ? multi_lds(q.k, kBvhBlock) : 0), stream,
-                           s, pts, n, d_count, q);
-        return;
-    }
-    if (kList)
-        hipLaunchKernelGGL((k_point_list_query<kStride, kMode == kNearListAll>), dim3(grid_for(n)), dim3(kBlock), multi_lds(q.k, kBlock),
-                           stream, s0.tris, s0.nt, pts, n, d_count, q);
-    else
-        hipLaunchKernelGGL((k_point_any_query<kStride>), dim3(grid_for(n)), dim3(kBlock), 0, stream, s0.tris, s0.nt, pts, n, d_count, q);
-}
 template <int kMode>
-void launch_near_stride(const DevScene &s, const void *pts, int32_t point_stride, int32_t n, const int32_t *d_count, const NearQuery &q,
-                        hipStream_t stream) {
-    if (point_stride == 4) launch_near_mode<4, kMode>(s, pts, n, d_count, q, stream);
-    else launch_near_mode<3, kMode>(s, pts, n, d_count, q, stream);
+void launch_near_mode(const DevScene &s, const void *pts, int32_t point_stride, int32_t n, const int32_t *d_count, const NearQuery &q,
+                      hipStream_t stream) {
+    constexpr bool kList = kMode != kNearAny;
+    for_stride(point_stride, [&](auto st) {
+        constexpr int kStride = st;
+        launch_query(s, n, kList ? multi_lds(q.k) : 0, stream, [](auto w, auto c) { return k_bvh_near_query<w, kStride, c, kMode>; },
+                     kList ? k_point_list_query<kStride, kMode == kNearListAll> : k_point_any_query<kStride>, pts, n, d_count, q);
+    });
 }
 }  // namespace
 
@@ -5632,15 +5588,15 @@ void launch_near_query(const DevScene &s, bool count_all, const void *pts, int32
                        const float *d_rmax, int32_t k, void *hits, int32_t *nfound, float *points, hipStream_t stream) {
     if (n <= 0) return;
     const NearQuery q{d_rmax, k, static_cast<int4 *>(hits), nfound, points, nullptr};
-    if (count_all) launch_near_stride<kNearListAll>(s, pts, point_stride, n, d_count, q, stream);
-    else launch_near_stride<kNearList>(s, pts, point_stride, n, d_count, q, stream);
+    if (count_all) launch_near_mode<kNearListAll>(s, pts, point_stride, n, d_count, q, stream);
+    else launch_near_mode<kNearList>(s, pts, point_stride, n, d_count, q, stream);
 }
 
 void launch_within_query(const DevScene &s, const void *pts, int32_t point_stride, int32_t n, const int32_t *d_count,
                          const float *d_rmax, uint8_t *within, hipStream_t stream) {
     if (n <= 0) return;
     const NearQuery q{d_rmax, 0, nullptr, nullptr, nullptr, within};
-    launch_near_stride<kNearAny>(s, pts, point_stride, n, d_count, q, stream);
+    launch_near_mode<kNearAny>(s, pts, point_stride, n, d_count, q, stream);
 }
 
 void launch_gen_rays_device(const void *org, const void *dst, int32_t ray_stride, int32_t n, const DevWork &w, hipStream_t stream) {

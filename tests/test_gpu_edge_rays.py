@@ -173,7 +173,7 @@ def test_occlusion_by_both_walks(plain, glassy, letter):
 def test_device_query_stack_overflow_area(plain, glassy, letter):
     """lds_stack 1: all but one entry of every lane's traversal stack lies in the device queries' own
     overflow area (ensure_stack_ovf: area index kMaxPipes, stack_entries - 1 rows of grid x block lanes;
-    launch_query_mode's grid is at most bvh_grid blocks, and a walk holds at most 3 entries per four-wide
+    launch_query's grid is at most bvh_grid blocks, and a walk holds at most 3 entries per four-wide
     level, 1 per binary level, whatever the floats are). Three copies of the class: more than one block, with
     far origins (every box wanted: the deepest stacks) next to each other in every wave."""
     o, d, _, want = glassy.rays(letter)
