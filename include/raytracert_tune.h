@@ -136,6 +136,16 @@ extern "C" {
                                     (default): always the launch after next (r02's double buffering). Measured
                                     neutral: C4 orbit one at a time 0.430-0.432 ms either way, cold and static
                                     frames equal (profiles/r06o_ab_order_early.txt). Placement only */
+#define RT_TUNE_DARK_LIGHTS 38    /* 1 (default): the chain launch walks no shadow ray to a light that cannot reach
+                                    the hit: a light whose diffuse and specular terms are exact zeros for the hit
+                                    (the hit faces away from the light and, for the specular term, from the camera
+                                    too, by a margin) while the hit's stored normal is a fixed point of the in-place
+                                    normalisations an unshadowed light makes, so the verdict can change neither the
+                                    colour nor the reflection ray (raytracert_amd/csrc/dark_lights.h). Ray counts
+                                    stay the reference's. At 1 a chain's first step is left alone (a hit that the
+                                    rays' own eye sees faces it and cannot be dark with the specular term on, and
+                                    the test then costs for nothing: C5 +0.4-0.8%); 2: the first step too (an eye
+                                    placed apart from the view). 0: every walk is made. Every byte equal under all */
 #define RT_TUNE_TOP_NODES 13     /* retired in r03 (0-85 accepted, no effect): an LDS copy of the four-wide
                                     tree's top levels; with float node rows loaded from global memory it
                                     measured slower (flat loads, 64-bit addresses) */

@@ -60,12 +60,15 @@ struct alignas(16) DevMaterial {
     float Kd[3]; float Ns;
     float Ka[3]; float Ni;
     float Ks[3]; float Tr;
-    uint32_t flags;
+    uint32_t flags;      // RT_HAS_* | kMatDarkOk
     float powf_nr2;      // glibc powf(1/Ni, 2)  (raytracing.cpp:302), precomputed on the host
     float powf_ni2;      // glibc powf(Ni, 2)    (raytracing.cpp:316)
     uint32_t transparent; // has_Tr && Tr < 1 (raytracing.cpp:254)
 };
 static_assert(sizeof(DevMaterial) == 64, "DevMaterial must be 64 bytes");
+// DevMaterial::flags, beside the RT_HAS_* bits: Kd, Ks and Tr are finite and, with Ks and Ns present, Ns is
+// finite and > 0 (dark_lights.h dark_material_ok), set by build_dev_materials
+constexpr uint32_t kMatDarkOk = 1u << 31;
 
 // ---- BVH (bvh.cpp) -------------------------------------------------------------------------
 constexpr int kMaxBvhDepth = 40;                 // builder bound = GPU traversal stack depth

@@ -112,6 +112,7 @@ struct DevScene {
     int32_t prio_batches;           // RT_TUNE_PRIORITY_BATCHES: longest batches run at raised wave priority
     int32_t shadow_helpers;         // RT_TUNE_SHADOW_HELPERS: split waves' idle lanes walk their owners' lights
     int32_t quad_walk;              // RT_TUNE_QUAD_WALK: the quarter tier's waves walk with four lanes per ray
+    int32_t dark_lights;            // RT_TUNE_DARK_LIGHTS: the chain launch walks no shadow ray to a light that cannot reach the hit
 };
 
 struct DevWork {

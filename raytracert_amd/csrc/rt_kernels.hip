@@ -25,6 +25,7 @@
 #include "rt_kernels.h"
 #include "lbvh_shared.h"
 #include "spec_pow.h"
+#include "dark_lights.h"
 
 namespace rt {
 namespace {
@@ -42,12 +43,7 @@ __device__ __forceinline__ V3 neg(V3 a) { return mk(-a.x, -a.y, -a.z); }
 __device__ __forceinline__ V3 scale(V3 a, float f) { return mk(a.x * f, a.y * f, a.z * f); }   // Vec3D.h:12-18
 __device__ __forceinline__ V3 mul(V3 a, V3 b) { return mk(a.x * b.x, a.y * b.y, a.z * b.z); }  // Vec3D.h:20-22
 __device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; } // Vec3D.h:192-194
-__device__ __forceinline__ void normalize(V3 &a) {                                                 // Vec3D.h:142-151
-    float len = sqrtf(dot(a, a));
-    if (len == 0.0f) return;
-    float rez = 1.0f / len;
-    a.x *= rez; a.y *= rez; a.z *= rez;
-}
+__device__ __forceinline__ void normalize(V3 &a) { normalize3(a.x, a.y, a.z); }                   // Vec3D.h:142-151 (dark_lights.h)
 __device__ __forceinline__ float max_std(float a, float b) { return (a < b) ? b : a; }            // std::max
 __device__ __forceinline__ V3 ld3(const float4 &v) { return mk(v.x, v.y, v.z); }
 
@@ -3236,6 +3232,88 @@ constexpr int kChainSteps = 256;   // max_lvl <= 254
 // 116 -> 72 MB per launch (profiles/r04_ab_opaque_args.txt). Reading the launch's scalar arguments
 // (outputs, first step, split tiers) that way too measured within the spread (profiles/r04_ab_opaque_args2.txt).
 
+// k_chain's explicit arguments as laid out in the kernel-argument segment (in order, each at its
+// natural alignment, as the members of a struct), for the opaque-argument reads. The layout is a property of
+// the kernel's signature, so it is checked once per kernel instantiation rather than per launch:
+// probe_chain_kernargs launches k_chain_kernarg_probe, a kernel with k_chain's exact parameter list,
+// which compares every argument with the ChainKernargs member at its place (chain_kernarg_mismatch)
+// and reports a bit per argument.
+#ifndef RT_KARGS_PERTURB
+#define RT_KARGS_PERTURB 0   // test build only (librtamd_kargperturb.so): a layout the probe must reject
+#endif
+struct ChainKernargs {
+    DevScene sc;
+    ShadeParams p;
+    DevWork w;
+#if RT_KARGS_PERTURB
+    int perturb;
+#endif
+    int first, ordered;
+    uint8_t *out_u8;
+    float *out_f32;
+    int fuse_spp, spb, nbatch;
+    FrameGeom g;
+    int split, split8;
+    FrameSet fs;
+};
+// the kernel-argument segment is at most 4 KB (the scene, the shading parameters with 16 lights, the
+// workspace, the frame geometry and the multi-frame set are 2,024 B now): growth past it fails here
+static_assert(sizeof(ChainKernargs) <= 4096, "k_chain's arguments exceed the 4 KB kernel-argument segment");
+
+// Dark lights (RT_TUNE_DARK_LIGHTS, dark_lights.h): the lights among `mine` (mask bits) that cannot reach the
+// hit (triangle idx at P), as mask bits. shade_hit's diffuse and specular terms for such a light are
+// exact zeros and its in-place normalisations leave the hit's normal as it is, so isShadow's verdict
+// changes nothing: the caller marks the light shadowed without walking its ray. In cost order: the view
+// compare (per hit), a dot per light, then the material and the lights' specular compares, then the
+// fixed point N^c(n0) == n0 with shade_hit's own normalize, once per hit. The rule
+// depends only on the hit, the light and the camera, so whichever lane evaluates it gets the same bit.
+// Everything here is dead before the first walk. The scene, the lights and the camera are read from the
+// kernel arguments through a pointer the compiler cannot follow (as k_chain reads them per batch), and the
+// triangle index goes behind an empty asm: otherwise the scalar loads are hoisted and held across the
+// walks, and the loads of the normal and the material are shared with shade_hit's and held too (9 more
+// spilled SGPRs and 4 B more scratch per lane in the timed kernels; tools/kernel_resources.sh and
+// profiles/dark_lights_kernel_resources.txt are the check after a compiler change).
+// PRECONDITION: the running kernel's arguments are ChainKernargs and the sc and p its caller holds are
+// ka->sc and ka->p unchanged. Only k_chain satisfies it; chain_step and chain_step_quad, the only callers,
+// are instantiated from k_chain alone. ChainArgsTag makes a call from anywhere else say so at the call.
+// `step`: with the knob at 1 (the default) a chain's first step is left alone: a hit the rays' own eye sees
+// faces it, so with the specular term on it cannot be dark, and the first steps are most of a frame's hits
+// (the rule then cost C5 0.4-0.8% for nothing); 2 tests every step (an eye apart from the view: the tests).
+struct ChainArgsTag {};
+__device__ __forceinline__ uint32_t dark_lights_mask(ChainArgsTag, int idx, V3 P, uint32_t mine, int step) {
+    typedef const __attribute__((address_space(4))) ChainKernargs *KargPtr;
+    KargPtr ka = (KargPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    const DevScene &sc = *(const DevScene *)&ka->sc;
+    if (sc.dark_lights == 0 || (sc.dark_lights == 1 && step == 0)) return 0;   // (wave-uniform)
+    const ShadeParams &p = *(const ShadeParams *)&ka->p;
+    asm volatile("" : "+v"(idx));
+    const float4 nw = sc.normals[idx];
+    const float n0[3] = {nw.x, nw.y, nw.z};
+    const float Pf[3] = {P.x, P.y, P.z};
+    // With the specular feature on, the view compare comes first: it is per hit, not per light, and no hit
+    // that faces the camera passes it, so such a hit costs the same however many lights there are. A material
+    // without Ks or Ns has no specular term and would not need it: its hits only lose skips, never exactness.
+    const bool spec_feature = (p.flags & RT_SPECULAR) != 0;   // (wave-uniform)
+    if (spec_feature && !dark_view(n0, Pf, p.cam)) return 0;
+    // (every light in turn, wave-uniform, so the lights are scalar operands; `mine` picks this lane's)
+    uint32_t cand = 0;
+    for (int l = 0; l < p.n_lights; ++l)
+        if (dark_light_side(n0, p.lnorm[l])) cand |= 1u << l;
+    cand &= mine;
+    if (cand == 0) return 0;
+    const uint32_t mf = sc.mats[sc.tri_mat[idx]].flags;
+    if (!(mf & kMatDarkOk)) return 0;
+    const bool diff_on = (p.flags & RT_DIFFUSE) && (mf & RT_HAS_KD);
+    const bool spec_on = (p.flags & RT_SPECULAR) && (mf & RT_HAS_KS) && (mf & RT_HAS_NS);
+    if (spec_on) {   // (the view compare: made above)
+        for (int l = 0; l < p.n_lights; ++l)
+            if (((cand >> l) & 1u) && !dark_spec_light(n0, Pf, p.lights[l])) cand &= ~(1u << l);
+        if (cand == 0) return 0;
+    }
+    return dark_fixed_point(n0, (diff_on ? 1 : 0) + (spec_on ? 1 : 0)) ? cand : 0;
+}
+
 template <bool kAnyHit, int W, bool kCount, bool kInLane = false, bool kSteal = false>
 __device__ __forceinline__ Secondary chain_step(const DevScene &sc, const ShadeParams &p, const DevWork &w, int step,
                                                 int sample, V3 org, V3 dst, int lvl, const LaneStack &stack, int *s_sh,
@@ -3288,14 +3366,44 @@ __device__ __forceinline__ Secondary chain_step(const DevScene &sc, const ShadeP
         }
         if (hit || role > 0) {
             if (role == 0) atomicAdd(&s_sh[step], p.n_lights);
+            // (s_sh keeps the reference's count: a dark light is an isShadow call it makes)
+            // this lane's lights, less the dark ones (marked shadowed without a walk), wait in the mask's upper
+            // half (the chain launch has at most RT_MAX_LIGHTS = 16 lights) and the walks loop over those bits:
+            // one register across the walks. (A skip inside a loop over every light, or the bits in a register
+            // of their own, cost 4 B more scratch per lane in the timed kernels.)
+            static_assert(RT_MAX_LIGHTS <= 16, "the lights to walk share the verdict mask's register");
             const V3 so = mk(bI.x + 0.1f, bI.y + 0.1f, bI.z + 0.1f);                // :248
-            for (int l = role; l < p.n_lights; l += G + 1) {
+            if (!kPair) {
+                // no helper roles: the lights in turn, wave-uniform (scalar operands, as before the rule); a lane
+                // whose light is dark sits the walk out (the stealing walk: it helps the others)
+                mask = dark_lights_mask(ChainArgsTag(), bidx, bI, (1u << p.n_lights) - 1u, step);
+                for (int l = 0; l < p.n_lights; ++l) {
+                    int sidx = -1;
+                    V3 sI = mk(0, 0, 0);
+                    const V3 Lp = light_at<false>(p.lights, p.light_ext, l);   // (the chain launch: <= RT_MAX_LIGHTS)
+                    const V3 sd = mk(Lp.x - so.x, Lp.y - so.y, Lp.z - so.z);
+                    bvh_query_w<kAnyHit, W, kSteal>(sc, so, sd, !((mask >> l) & 1u), sidx, sI, stack, ws.tests, ws.visits);
+                    if (sidx >= 0 && !sc.mats[sc.tri_mat[sidx]].transparent) mask |= 1u << l;   // :253-257
+                }
+            } else {
+            uint32_t mine = (1u << p.n_lights) - 1u;
+            if (G > 0) {   // (wave-uniform)
+                mine = 0;
+                for (int l = role; l < p.n_lights; l += G + 1) mine |= 1u << l;
+            }
+            mask = dark_lights_mask(ChainArgsTag(), bidx, bI, mine, step);
+            mask |= (mine & ~mask) << 16;
+            while (mask >> 16) {   // (the light's index is per lane here, as the role made it before the rule)
+                const int l = __ffs(static_cast<int>(mask >> 16)) - 1;
                 int sidx = -1;
                 V3 sI = mk(0, 0, 0);
                 const V3 Lp = light_at<false>(p.lights, p.light_ext, l);   // (the chain launch: <= RT_MAX_LIGHTS)
                 const V3 sd = mk(Lp.x - so.x, Lp.y - so.y, Lp.z - so.z);
                 bvh_query_w<kAnyHit, W, kSteal>(sc, so, sd, true, sidx, sI, stack, ws.tests, ws.visits);
-                if (sidx >= 0 && !sc.mats[sc.tri_mat[sidx]].transparent) mask |= 1u << l;   // :253-257
+                const uint32_t bit = (mask >> 16) & (0u - (mask >> 16));   // this light's, lowest of those waiting
+                if (sidx >= 0 && !sc.mats[sc.tri_mat[sidx]].transparent) mask |= bit;   // :253-257
+                mask ^= bit << 16;
+            }
             }
         }
         for (int r = 0; r < G; ++r) {   // an owner's helpers' verdicts (ranks rk, rk + nh, ... among the others)
@@ -3327,14 +3435,19 @@ __device__ __forceinline__ Secondary chain_step_quad(const DevScene &sc, const S
     uint32_t mask = 0;   // isShadow per light (:241-261)
     if ((p.flags & RT_SHADOWS) && p.n_lights > 0) {
         if (q == 0) atomicAdd(&s_sh[step], p.n_lights);
+        mask = dark_lights_mask(ChainArgsTag(), bidx, bI, (1u << p.n_lights) - 1u, step);   // (the same bits on the quad's four lanes)
+        mask |= (((1u << p.n_lights) - 1u) & ~mask) << 16;   // the lights to walk (chain_step): not the dark ones
         const V3 so = mk(bI.x + 0.1f, bI.y + 0.1f, bI.z + 0.1f);                // :248
-        for (int l = 0; l < p.n_lights; ++l) {
+        while (mask >> 16) {
+            const int l = __ffs(static_cast<int>(mask >> 16)) - 1;
             int sidx = -1;
             V3 sI = mk(0, 0, 0);
             const V3 Lp = light_at<false>(p.lights, p.light_ext, l);
             const V3 sd = mk(Lp.x - so.x, Lp.y - so.y, Lp.z - so.z);
             bvh4_query_quad<kAnyHit>(sc, so, sd, true, sidx, sI, st, ws.tests, ws.visits, q, qshift);
-            if (sidx >= 0 && !sc.mats[sc.tri_mat[sidx]].transparent) mask |= 1u << l;   // :253-257
+            const uint32_t bit = (mask >> 16) & (0u - (mask >> 16));
+            if (sidx >= 0 && !sc.mats[sc.tri_mat[sidx]].transparent) mask |= bit;   // :253-257
+            mask ^= bit << 16;
         }
     }
     return shade_hit<true, false>(sc, p, w, step, sample, ray, lvl, bidx, bI, [&](int l) { return ((mask >> l) & 1u) != 0; });
@@ -3426,34 +3539,6 @@ __device__ __forceinline__ void quad_batch(const DevScene &sc, const ShadeParams
     acc = mk(acc.x / div, acc.y / div, acc.z / div);   // operator/, Vec3D.h:36-38
     if (sl == pix_sl && q == 0 && px >= 0) store_pixel(acc, 3 * static_cast<int64_t>(px), out_u8, out_f32);
 }
-
-// k_chain's explicit arguments as laid out in the kernel-argument segment (in order, each at its
-// natural alignment, as the members of a struct), for the opaque-argument reads. The layout is a property of
-// the kernel's signature, so it is checked once per kernel instantiation rather than per launch:
-// probe_chain_kernargs launches k_chain_kernarg_probe, a kernel with k_chain's exact parameter list,
-// which compares every argument with the ChainKernargs member at its place (chain_kernarg_mismatch)
-// and reports a bit per argument.
-#ifndef RT_KARGS_PERTURB
-#define RT_KARGS_PERTURB 0   // test build only (librtamd_kargperturb.so): a layout the probe must reject
-#endif
-struct ChainKernargs {
-    DevScene sc;
-    ShadeParams p;
-    DevWork w;
-#if RT_KARGS_PERTURB
-    int perturb;
-#endif
-    int first, ordered;
-    uint8_t *out_u8;
-    float *out_f32;
-    int fuse_spp, spb, nbatch;
-    FrameGeom g;
-    int split, split8;
-    FrameSet fs;
-};
-// the kernel-argument segment is at most 4 KB (the scene, the shading parameters with 16 lights, the
-// workspace, the frame geometry and the multi-frame set are 2,024 B now): growth past it fails here
-static_assert(sizeof(ChainKernargs) <= 4096, "k_chain's arguments exceed the 4 KB kernel-argument segment");
 
 // Bit k set: argument k of k_chain is not where ChainKernargs places it. The probe launch fills each
 // by-value structure with a word pattern (word i of argument k = kKargTag[k] + i, padding included,

@@ -23,6 +23,7 @@
 #include <cstring>
 #include <unordered_map>
 
+#include "dark_lights.h"
 #include "rt_internal.h"
 
 namespace rt {
@@ -330,6 +331,8 @@ void build_dev_materials(const HostScene &s, std::vector<DevMaterial> &out) {
         d.powf_nr2 = std::pow(nr, static_cast<float>(two));
         d.powf_ni2 = std::pow(m.Ni, static_cast<float>(two));
         d.transparent = ((m.flags & RT_HAS_TR) && m.Tr < 1.0f) ? 1u : 0u;
+        d.flags &= ~kMatDarkOk;
+        if (dark_material_ok(m.Kd, m.Ks, m.Tr, m.Ns, (m.flags & RT_HAS_KS) && (m.flags & RT_HAS_NS))) d.flags |= kMatDarkOk;
     }
 }
 
