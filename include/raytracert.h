@@ -30,6 +30,9 @@
  *                         mesh, by crossing parity along an axis, and the closest-point record with that sign)
  *   rt_box_overlap_device / rt_box_occupied_device  (extensions: the triangles that meet each axis-aligned query
  *                         box, lowest indices first, and whether any does)
+ *   rt_triangle_overlap_device / rt_triangle_collides_device  (extensions: the triangles that meet each query
+ *                         triangle, lowest indices first, and whether any does; with a self index, the scene's
+ *                         own self-intersections)
  *   rt_debug_trace       debug key 'd' (shoot + trace)     raytracing.cpp:493-510
  *                         (batched; also trace(o,d,lvl) at lvl 0, raytracing.h:30)
  *   rt_render_tile        the 'r'-key frame loop            main.cpp:340-411 (loop :355-395,
@@ -547,6 +550,60 @@ int rt_box_overlap_device(rt_scene *scene, const void *d_lo, const void *d_hi, i
  * entry above. */
 int rt_box_occupied_device(rt_scene *scene, const void *d_lo, const void *d_hi, int32_t box_stride, int32_t n,
                            const void *d_count, uint32_t flags, void *d_occupied_out /* n x uint8 */, void *stream);
+/* The triangles that meet each query triangle, from one walk: the narrow phase of mesh against mesh. d_qtris holds
+ * 3 n vertices, query-major: vertex 3 i + j is Q_j of query i, laid out as d_origins of the ray entries (tri_stride
+ * RT_RAYS_PACKED: 36 bytes per triangle, 4-byte aligned; RT_RAYS_PADDED: three float4 per triangle, 16-byte aligned,
+ * w ignored). d_count, stream, the ordering against updates, rebuilds, rt_scene_set_mesh and rt_scene_destroy, rows
+ * at or past the live count, k, d_after, d_tris_out (ascending indices, then -1), d_nfound_out (min(m, k), or m with
+ * RT_TRI_COUNT_ALL) and paging by after_i are rt_box_overlap_device's, with "query triangle" for "box": m is the number
+ * of candidates of query i that overlap it (below), whose index is greater than after_i, and that self_i does not
+ * pass over.
+ * d_self (n x int32, 4-byte aligned, may be NULL): self_i in [0, nt) names a scene triangle; candidate t is then
+ * passed over when t == self_i or when any of tri_v[3 t .. 3 t + 2] equals any of tri_v[3 self_i .. 3 self_i + 2]
+ * (index compares, no geometry). Any other value, and a NULL array, passes nothing over. With query i = scene
+ * triangle i, self_i = i and after_i = i, the lists are every intersecting pair of triangles without a common
+ * vertex index, each pair exactly once (at its lower index). A triangle folded onto its own neighbour is therefore
+ * not reported, and neither are duplicated vertices that carry different indices treated as shared.
+ *
+ * The definition. The candidates are rt_box_overlap_device's: every triangle whose record normal is not (0,0,0).
+ * V_j = xyz[tri_v[3 t + j]], the scene's current vertex array entries. No contraction anywhere.
+ *   0. a query with a NaN or infinite component is empty: m = 0
+ *   1. raw compares, no arithmetic: qlo_a = min_j Q_j[a], qhi_a = max_j Q_j[a]; separated if on some axis a every
+ *      V_j[a] > qhi_a, or every V_j[a] < qlo_a
+ *   2. from here on everything is binary64: u_j[a] = (double)Q_j[a] - (double)Q_0[a] (so u_0 = 0) and
+ *      v_j[a] = (double)V_j[a] - (double)Q_0[a]; there is no binary32 centring
+ *   3. the edges e_0 = u_1 - u_0, e_1 = u_2 - u_1, e_2 = u_0 - u_2, and f_0, f_1, f_2 the same on v; x cross y is
+ *      [a] = x[b] * y[c] - x[c] * y[b] with (b, c) = ((a + 1) % 3, (a + 2) % 3); n_Q = e_0 cross e_1,
+ *      n_V = f_0 cross f_1. A query whose n_Q is exactly (0,0,0) is empty: m = 0 (points and segments have other
+ *      entries)
+ *   4. seventeen axes w: n_Q, n_V, the nine e_i cross f_j, the three n_Q cross e_i and the three n_V cross f_j (these
+ *      six decide coplanar pairs). Per axis p_j = (w[0] u_j[0] + w[1] u_j[1]) + w[2] u_j[2] and q_j the same on v_j
+ *      (j = 0, 1, 2); separated if every p_i < every q_j (nine compares joined by &&), or every p_i > every q_j
+ * A candidate overlaps exactly when neither step 1 nor any axis separates it. All compares are strict, so touching
+ * is overlap, and a NaN separates nothing. The verdict is an OR over the axes: the order in which an implementation
+ * evaluates them, and whether it stops at the first that separates, changes nothing.
+ * Consequences: as for the box entry, step 1 lets a tree walk skip a child exactly when the query's bounds
+ * [qlo, qhi] and the child's box are disjoint on some axis, with no margin: the result is the list of the loop over
+ * every triangle, on any builder, either tree width, after any refit. Coordinates are assumed small enough that the
+ * differences and products of steps 2 to 4 do not overflow binary64.
+ * The verdict is exact (the closed triangles meet) wherever the binary64 products and sums are exact, for example
+ * on coordinates that are multiples of 2^-4 within +-3. Elsewhere a verdict that differs from the exact one needs a
+ * pair within rounding of touching, about 2^-40 of the largest coordinate magnitude; there it is deterministic but
+ * not guaranteed.
+ * Errors in rt_box_overlap_device's order: RT_E_NODEV on a host-only scene before anything else; RT_E_ARG for a NULL
+ * scene, n < 0, a bad stride, a NULL or misaligned array, k out of range, any flag but RT_TRI_COUNT_ALL, that flag
+ * with a NULL d_nfound_out, n * k above INT32_MAX; n == 0 returns RT_OK with nothing enqueued. */
+#define RT_TRI_COUNT_ALL (1u << 4)   /* d_nfound_out = every overlapping candidate past `after`, not min(m, k) */
+int rt_triangle_overlap_device(rt_scene *scene, const void *d_qtris, int32_t tri_stride, int32_t n,
+                               const void *d_count, const void *d_after /* n x int32, may be NULL */,
+                               const void *d_self /* n x int32, may be NULL */, uint32_t flags, int32_t k,
+                               void *d_tris_out /* n x k int32 */, void *d_nfound_out /* n x int32 */, void *stream);
+/* Whether anything meets the query triangle: d_collides_out[i] (n x uint8) is 1 when m > 0 (after_i = -1, self_i as
+ * given) and 0 otherwise; the walk leaves a query at its first overlapping candidate. flags must be 0 (RT_E_ARG
+ * otherwise). Everything else as the entry above. */
+int rt_triangle_collides_device(rt_scene *scene, const void *d_qtris, int32_t tri_stride, int32_t n,
+                                const void *d_count, const void *d_self /* may be NULL */, uint32_t flags,
+                                void *d_collides_out /* n x uint8 */, void *stream);
 /* performRayTracing (raytracing.cpp:410-416) for rays in device memory: d_rgb_out[3*i..] (3n packed floats),
  * bit for bit rt_trace_rays' rgb_out. counts as in rt_trace_rays; non-NULL synchronises the stream. Uses
  * render pipeline 0's workspace (ordered against the frames that use it): returns after enqueueing when

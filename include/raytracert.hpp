@@ -257,6 +257,18 @@ class RayTracer {
                              void *d_occupied_out, void *stream) {
         check(rt_box_occupied_device(scene_, d_lo, d_hi, box_stride, n, d_count, flags, d_occupied_out, stream));
     }
+    // the triangles that meet each query triangle, lowest indices first (rt_triangle_overlap_device: d_qtris 3 n vertices,
+    // d_after and d_self n int32 or null, d_tris_out n x k int32, d_nfound_out n int32 or null; flags: RT_TRI_COUNT_ALL)
+    void triangle_overlap_device(const void *d_qtris, int32_t tri_stride, int32_t n, const void *d_count, const void *d_after,
+                                 const void *d_self, uint32_t flags, int32_t k, void *d_tris_out, void *d_nfound_out, void *stream) {
+        check(rt_triangle_overlap_device(scene_, d_qtris, tri_stride, n, d_count, d_after, d_self, flags, k, d_tris_out, d_nfound_out,
+                                         stream));
+    }
+    // whether a triangle meets each query triangle (rt_triangle_collides_device: d_collides_out n x uint8; flags 0)
+    void triangle_collides_device(const void *d_qtris, int32_t tri_stride, int32_t n, const void *d_count, const void *d_self,
+                                  uint32_t flags, void *d_collides_out, void *stream) {
+        check(rt_triangle_collides_device(scene_, d_qtris, tri_stride, n, d_count, d_self, flags, d_collides_out, stream));
+    }
     void perform_ray_tracing_device(const void *d_origins, const void *d_dests, int32_t ray_stride, int32_t n, void *d_rgb_out,
                                     void *stream, uint64_t counts[3] = nullptr) {
         rt_params p = params();

@@ -68,6 +68,7 @@ RANGE_TO_DEST, OCCLUDE_ANY_OPAQUE = 1 << 0, 1 << 1   # flags of the ranged devic
 MULTI_HIT_MAX, MULTI_COUNT_ALL = 16, 1 << 2           # rt_multi_hit_range_device: largest k; its count flag
 NEAR_COUNT_ALL = 1 << 3                               # rt_nearest_triangles_device: its count flag
 BOX_COUNT_ALL = 1 << 4                                # rt_box_overlap_device: its count flag
+TRI_COUNT_ALL = 1 << 4                                # rt_triangle_overlap_device: its count flag
 AXIS_POS_X, AXIS_NEG_X, AXIS_POS_Y, AXIS_NEG_Y, AXIS_POS_Z, AXIS_NEG_Z = range(6)   # rt_point_inside_device directions
 HIT_BYTES = 16                          # sizeof(rt_hit): int32 triangle, float distance, s, t
 UPDATE_AUTO, UPDATE_REBUILD = 0, 1      # rt_scene_update_vertices modes
@@ -150,6 +151,8 @@ _SIGNATURES = {
     "rt_signed_distance_device": ([_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, C.c_uint32, _VP, _VP, _VP, _VP], C.c_int),
     "rt_box_overlap_device": ([_VP, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP, C.c_uint32, C.c_int32, _VP, _VP, _VP], C.c_int),
     "rt_box_occupied_device": ([_VP, _VP, _VP, C.c_int32, C.c_int32, _VP, C.c_uint32, _VP, _VP], C.c_int),
+    "rt_triangle_overlap_device": ([_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_uint32, C.c_int32, _VP, _VP, _VP], C.c_int),
+    "rt_triangle_collides_device": ([_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, C.c_uint32, _VP, _VP], C.c_int),
     "rt_trace_rays_device": ([_VP, C.POINTER(RtParams), _VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP], C.c_int),
     "rt_debug_trace": ([_VP, C.POINTER(RtParams), _VP, _VP, _VP, C.c_int32, C.POINTER(C.c_int32), _VP], C.c_int),
     "rt_render_tile": ([_VP, C.POINTER(RtParams), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP], C.c_int),

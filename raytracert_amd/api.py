@@ -670,6 +670,79 @@ class Scene:
                                            C.c_void_p(occ.data_ptr()), self._stream_ptr(stream)))
         return occ[:n]
 
+    def _device_tris(self, name: str, tris):
+        """Checks before anything touches a device: (n, tri_stride) of a CUDA float32 tensor of query triangles."""
+        import torch
+        if not isinstance(tris, torch.Tensor):
+            raise ValueError(f"{name}: tris must be a CUDA torch tensor (there is no host method)")
+        if tris.dtype != torch.float32:
+            raise ValueError(f"{name}: tris must be float32, not {tris.dtype}")
+        if tris.dim() != 3 or tris.shape[1] != 3 or tris.shape[2] not in (_capi.RAYS_PACKED, _capi.RAYS_PADDED):
+            raise ValueError(f"{name}: tris must have shape (n, 3, 3) or (n, 3, 4), not {tuple(tris.shape)}")
+        if not tris.is_contiguous():
+            raise ValueError(f"{name}: tris must be contiguous")
+        if not tris.is_cuda:
+            raise ValueError(f"{name}: tris is a CPU tensor (there is no host method)")
+        if tris.device.index != self.device:
+            raise ValueError(f"{name}: tris is on {tris.device}, the scene on device {self.device}")
+        return int(tris.shape[0]), int(tris.shape[2])
+
+    def _device_index(self, name: str, what: str, t, n: int):
+        """A per-query index array (after, self_index): None, or a contiguous CUDA int32 tensor of n (or more) elements."""
+        import torch
+        if t is None:
+            return None
+        if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != self.device or t.dtype != torch.int32
+                or t.dim() != 1 or not t.is_contiguous() or t.shape[0] < n):
+            raise ValueError(f"{name}: {what} must be a contiguous CUDA int32 tensor of shape (>= {n},) on the scene's device")
+        return C.c_void_p(t.data_ptr())
+
+    def triangle_overlap_device(self, tris, k: int, after=None, self_index=None, count=None, count_all: bool = False, out=None,
+                                stream=None):
+        """rt_triangle_overlap_device: per query triangle (closed; include/raytracert.h states the arithmetic), the k
+        (1.._capi.MULTI_HIT_MAX) lowest indices of the candidate triangles that overlap it, ascending, from one walk.
+        tris: a contiguous CUDA float32 tensor (n, 3, 3) or (n, 3, 4) (w ignored); count and stream as
+        closest_point_device. after: an optional CUDA int32 tensor of n elements; only triangles with a greater index
+        are listed and counted (pass the last index received to page through a crowded query). self_index: an optional
+        CUDA int32 tensor of n elements; where it names a scene triangle, that triangle and every triangle sharing a
+        vertex index with it are passed over (any other value passes nothing over). With tris the scene's own
+        triangles and self_index = after = arange(n) the lists are the mesh's self-intersections, each pair once.
+        Returns (tris[n, k] int32, nfound[n] int32): rows past a query's triangles hold -1; nfound is the number of rows
+        that hold a triangle, or with count_all the number of overlapping candidates past `after` (which may exceed
+        k). A query with a non-finite component or of zero area is empty. out: a (tris, nfound) pair to write into,
+        (>= n, k) int32 and (>= n,) int32; the result is then views of them."""
+        import torch
+        name = "triangle_overlap_device"
+        if not isinstance(k, int) or isinstance(k, bool) or k < 1 or k > _capi.MULTI_HIT_MAX:
+            raise ValueError(f"{name}: k must be an int in [1, {_capi.MULTI_HIT_MAX}], not {k!r}")
+        n, stride = self._device_tris(name, tris)
+        cnt = self._device_count(name, count)
+        aft = self._device_index(name, "after", after, n)
+        slf = self._device_index(name, "self_index", self_index, n)
+        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
+            raise ValueError(f"{name}: out must be a (tris, nfound) pair")
+        found = self._device_out(name, None if out is None else out[0], n, torch.int32, (k,), -1, count is not None)
+        nf = self._device_out(name, None if out is None else out[1], n, torch.int32, (), 0, count is not None)
+        check(lib().rt_triangle_overlap_device(self._h, C.c_void_p(tris.data_ptr()), stride, n, cnt, aft, slf,
+                                               _capi.TRI_COUNT_ALL if count_all else 0, k, C.c_void_p(found.data_ptr()),
+                                               C.c_void_p(nf.data_ptr()), self._stream_ptr(stream)))
+        return found[:n], nf[:n]
+
+    def triangle_collides_device(self, tris, self_index=None, count=None, out=None, stream=None):
+        """rt_triangle_collides_device: collides[n] uint8, 1 where a candidate triangle overlaps the query triangle
+        (where triangle_overlap_device with the same self_index lists a triangle), else 0; the walk leaves a query at
+        the first such triangle. tris, self_index, count and stream as triangle_overlap_device; out: a (>= n,) uint8
+        tensor to write into."""
+        import torch
+        name = "triangle_collides_device"
+        n, stride = self._device_tris(name, tris)
+        cnt = self._device_count(name, count)
+        slf = self._device_index(name, "self_index", self_index, n)
+        col = self._device_out(name, out, n, torch.uint8, (), 0, count is not None)
+        check(lib().rt_triangle_collides_device(self._h, C.c_void_p(tris.data_ptr()), stride, n, cnt, slf, 0,
+                                                C.c_void_p(col.data_ptr()), self._stream_ptr(stream)))
+        return col[:n]
+
     def closest_point(self, points, rmax=None):
         """rt_closest_point for numpy arrays: returns (triangle[n] int32, distance[n] float32, st[n, 2] float32,
         point[n, 3] float32), closest_point_device's bits. rmax: optional n search radii."""

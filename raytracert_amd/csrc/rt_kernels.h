@@ -262,6 +262,17 @@ void launch_box_query(const DevScene &s, const float *xyz, const uint32_t *tri_v
 // rt_box_occupied_device: occupied[n] = 1 when a candidate overlaps the box, else 0 (the any mode of the same walk).
 void launch_box_occupied(const DevScene &s, const float *xyz, const uint32_t *tri_v, const void *lo, const void *hi, int32_t box_stride,
                          int32_t n, const int32_t *d_count, uint8_t *occupied, hipStream_t stream);
+// Triangle-overlap device query (rt_triangle_overlap_device): per query triangle (qtris: 3n vertices, query-major, in
+// the ray entries' layouts) the list and count of launch_box_query for the candidate triangles that overlap it; self[n]
+// (null: none) names a scene triangle that is passed over together with every triangle sharing a vertex index with
+// it (a value outside [0, s.nt) passes nothing over). The tree walk (k_bvh_tri) and the loop over every triangle
+// (k_tri) give the same bytes.
+void launch_tri_query(const DevScene &s, const float *xyz, const uint32_t *tri_v, bool count_all, const void *qtris, int32_t tri_stride,
+                      int32_t n, const int32_t *d_count, const int32_t *after, const int32_t *self, int32_t k, int32_t *tris_out,
+                      int32_t *nfound, hipStream_t stream);
+// rt_triangle_collides_device: collides[n] = 1 when a candidate overlaps the query triangle, else 0 (the any mode).
+void launch_tri_collides(const DevScene &s, const float *xyz, const uint32_t *tri_v, const void *qtris, int32_t tri_stride, int32_t n,
+                         const int32_t *d_count, const int32_t *self, uint8_t *collides, hipStream_t stream);
 // launch_gen_rays from the caller's device arrays in either layout (rt_trace_rays_device)
 void launch_gen_rays_device(const void *org, const void *dst, int32_t ray_stride, int32_t n, const DevWork &w,
                             hipStream_t stream);

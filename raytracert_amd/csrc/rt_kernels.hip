@@ -2387,24 +2387,37 @@ __device__ __forceinline__ bool box_eval(const BoxQuery &q, const TriRec *__rest
     return !(sep || d > r || d < -r);
 }
 
+// What a walk of this family evaluates at a leaf. A Leaf names the query's arguments (Query), one query as the walk
+// holds it (State: lo and hi are the corners the child test compares) and eval(q, tris, idx, state): whether triangle
+// idx is a candidate that overlaps, after any filter of the query's own. The box queries' Leaf; the triangle
+// queries' is TriLeaf, below.
+struct BoxLeaf {
+    using Query = BoxQuery;
+    using State = QBox;
+    static __device__ __forceinline__ bool eval(const BoxQuery &q, const TriRec *__restrict__ tris, int idx, const QBox &b) {
+        return box_eval(q, tris, idx, b);
+    }
+};
+
 // One triangle of a walk: the index filter, then the evaluation. kBoxAny: found is set and nothing else changes.
-template <int kMode>
-__device__ __forceinline__ void box_visit(const BoxQuery &q, const TriRec *__restrict__ tris, int idx, const QBox &b, int after, BoxList &bl,
-                                          bool &found) {
+template <int kMode, typename Leaf>
+__device__ __forceinline__ void box_visit(const typename Leaf::Query &q, const TriRec *__restrict__ tris, int idx,
+                                          const typename Leaf::State &b, int after, BoxList &bl, bool &found) {
     if (kMode == kBoxAny) {
-        if (!found && box_eval(q, tris, idx, b)) found = true;
+        if (!found && Leaf::eval(q, tris, idx, b)) found = true;
         return;
     }
     if (idx <= after || (kMode == kBoxList && idx > bl.bound)) return;
-    if (box_eval(q, tris, idx, b)) bl.admit(idx);
+    if (Leaf::eval(q, tris, idx, b)) bl.admit(idx);
 }
 
-template <int W, int kMode>
-__device__ __forceinline__ void bvh_box_walk(const DevScene &sc, const BoxQuery &q, const QBox &b, bool walk, int after, BoxList &bl,
-                                             bool &found, const LaneStack &stack, unsigned &tests, unsigned &visits) {
+template <int W, int kMode, typename Leaf>
+__device__ __forceinline__ void bvh_box_walk(const DevScene &sc, const typename Leaf::Query &q, const typename Leaf::State &b, bool walk,
+                                             int after, BoxList &bl, bool &found, const LaneStack &stack, unsigned &tests,
+                                             unsigned &visits) {
     // the always list: every lane (one whose box is empty takes nothing from it)
     for (int i = 0; i < sc.n_always; ++i)
-        if (walk) box_visit<kMode>(q, sc.tris, static_cast<int>(sc.always[i]), b, after, bl, found);
+        if (walk) box_visit<kMode, Leaf>(q, sc.tris, static_cast<int>(sc.always[i]), b, after, bl, found);
     tests += static_cast<unsigned>(max(sc.n_always, 0));
     if (!walk || found) return;
     if constexpr (W == 2) {
@@ -2417,12 +2430,12 @@ __device__ __forceinline__ void bvh_box_walk(const DevScene &sc, const BoxQuery 
                 // the original index, then tri_v and xyz: the leaf-ordered records do not hold V1, V2
                 if (kMode == kBoxAny) {
                     for (int k = 0; k < cnt && !found; ++k) {
-                        box_visit<kMode>(q, sc.tris, static_cast<int>(sc.leaf_idx[first + k]), b, after, bl, found);
+                        box_visit<kMode, Leaf>(q, sc.tris, static_cast<int>(sc.leaf_idx[first + k]), b, after, bl, found);
                         ++tests;
                     }
                     return found;
                 }
-                for (int k = 0; k < cnt; ++k) box_visit<kMode>(q, sc.tris, static_cast<int>(sc.leaf_idx[first + k]), b, after, bl, found);
+                for (int k = 0; k < cnt; ++k) box_visit<kMode, Leaf>(q, sc.tris, static_cast<int>(sc.leaf_idx[first + k]), b, after, bl, found);
                 tests += static_cast<unsigned>(cnt);
                 return false;
             });
@@ -2460,12 +2473,12 @@ __device__ __forceinline__ void bvh_box_walk(const DevScene &sc, const BoxQuery 
             // the original index, then tri_v and xyz: the leaf-ordered records do not hold V1, V2
             if (kMode == kBoxAny) {
                 for (int k = 0; k < cnt && !found; ++k) {
-                    box_visit<kMode>(q, sc.tris, static_cast<int>(sc.leaf_idx[first + k]), b, after, bl, found);
+                    box_visit<kMode, Leaf>(q, sc.tris, static_cast<int>(sc.leaf_idx[first + k]), b, after, bl, found);
                     ++tests;
                 }
                 if (found) return;
             } else {
-                for (int k = 0; k < cnt; ++k) box_visit<kMode>(q, sc.tris, static_cast<int>(sc.leaf_idx[first + k]), b, after, bl, found);
+                for (int k = 0; k < cnt; ++k) box_visit<kMode, Leaf>(q, sc.tris, static_cast<int>(sc.leaf_idx[first + k]), b, after, bl, found);
                 tests += static_cast<unsigned>(cnt);
             }
         }
@@ -2475,8 +2488,8 @@ __device__ __forceinline__ void bvh_box_walk(const DevScene &sc, const BoxQuery 
 }
 
 // The rows of one box: the list in order, then -1.
-template <int kMode>
-__device__ __forceinline__ void store_box(const BoxList &bl, int j, const BoxQuery &q) {
+template <int kMode, typename Query>
+__device__ __forceinline__ void store_box(const BoxList &bl, int j, const Query &q) {
     const size_t row0 = static_cast<size_t>(j) * static_cast<size_t>(bl.k);
     auto entry = [&](int i) { return i < bl.cnt ? bl.idx[i * bl.width] : -1; };
     if ((bl.k & 3) == 0 && (reinterpret_cast<uintptr_t>(q.tris_out) & 15) == 0) {   // (wave-uniform) rows of whole 16-byte stores
@@ -2514,7 +2527,7 @@ __global__ __launch_bounds__(kBvhBlock) void k_bvh_box(const DevScene sc, const 
         bl.k = kMode == kBoxAny ? 0 : q.k;
         bool found = false;
         wt.begin();
-        bvh_box_walk<W, kMode>(sc, q, b, walk, after, bl, found, stack, wt.tests, wt.visits);
+        bvh_box_walk<W, kMode, BoxLeaf>(sc, q, b, walk, after, bl, found, stack, wt.tests, wt.visits);
         wt.end();
         if (!active) return;
         if (kMode == kBoxAny) q.occupied[j] = found ? 1 : 0;
@@ -2543,10 +2556,260 @@ __global__ __launch_bounds__(kBlock) void k_box(const TriRec *__restrict__ tris,
     bool found = !walk;         // (kBoxAny) a lane whose box is empty has nothing to look for
     for (int i = 0; i < nt; ++i) {
         if (kMode == kBoxAny && (i & 15) == 0 && __all(found)) break;
-        if (walk) box_visit<kMode>(q, tris, i, b, after, bl, found);
+        if (walk) box_visit<kMode, BoxLeaf>(q, tris, i, b, after, bl, found);
     }
     if (!active) return;
     if (kMode == kBoxAny) q.occupied[j] = walk && found ? 1 : 0;
+    else store_box<kMode>(bl, j, q);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Triangle-overlap queries (rt_triangle_overlap_device, rt_triangle_collides_device): per query triangle the
+// candidate triangles (record normal not (0,0,0)) that meet it, with the box queries' lists, counts, `after` and
+// verdict, and a `self` index whose triangle and its neighbours (any shared vertex index) are passed over.
+// include/raytracert.h states the arithmetic; tri_eval is that statement op for op: step 1 compares the candidate's
+// vertices raw with the query's bounds, everything after it is binary64 on coordinates relative to the query's
+// first vertex, and the seventeen axes of the separating-axis test (two normals, nine edge pairs, six in-plane
+// edge normals) are each nine strict compares one way or nine the other, so touching is overlap and a NaN
+// separates nothing. The verdict is an OR over the axes: tri_eval leaves after the two normals and after the nine
+// edge pairs when one of them has separated, which changes no result.
+// The walk is the box queries' (bvh_box_walk on TriLeaf): the child test is theirs on the query's bounds, with no
+// margin for the same reason (step 1 is part of the definition and every box of the tree contains its triangles'
+// vertices); the list is BoxList. k_tri evaluates every triangle in index order.
+// ---------------------------------------------------------------------------------------------
+struct TriQuery {
+    const float *xyz;           // the scene's vertices (3 per vertex) and
+    const uint32_t *tri_v;      // triangles (3 per triangle): what the current records were built from
+    int32_t nt;                 // the scene's triangle count (what a self index is checked against)
+    const int32_t *after;       // per query, or null (-1)
+    const int32_t *self;        // per query, or null (nothing passed over)
+    int32_t k;
+    int32_t *tris_out;          // [n][k] (list modes)
+    int32_t *nfound;            // [n], or null
+    uint8_t *collides;          // [n] (kBoxAny)
+};
+
+// One query triangle: its bounds (step 1, and the walk's child test), its vertices, and the vertex indices of its
+// self triangle (self < 0: none).
+struct QTri {
+    V3 lo, hi;
+    V3 q0, q1, q2;
+    int self;
+    uint32_t s0, s1, s2;
+};
+
+__device__ __forceinline__ void cross64(const double (&x)[3], const double (&y)[3], double (&o)[3]) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const int bb = (a + 1) % 3, cc = (a + 2) % 3;
+        o[a] = x[bb] * y[cc] - x[cc] * y[bb];
+    }
+}
+
+// Whether axis w separates the triangles u and v: every p_i below every q_j, or every p_i above every q_j.
+__device__ __forceinline__ bool tri_axis(const double (&w)[3], const double (&u)[3][3], const double (&v)[3][3]) {
+    double p[3], q[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        p[j] = (w[0] * u[j][0] + w[1] * u[j][1]) + w[2] * u[j][2];
+        q[j] = (w[0] * v[j][0] + w[1] * v[j][1]) + w[2] * v[j][2];
+    }
+    bool below = true, above = true;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            below = below && p[i] < q[j];
+            above = above && p[i] > q[j];
+        }
+    return below || above;
+}
+
+// u_j = Q_j - Q_0 and the edges e of the query triangle, binary64 (steps 2 and 3 on the query's side)
+__device__ __forceinline__ void tri_query_edges(const QTri &t, double (&u)[3][3], double (&e)[3][3]) {
+    const float Q[3][3] = {{t.q0.x, t.q0.y, t.q0.z}, {t.q1.x, t.q1.y, t.q1.z}, {t.q2.x, t.q2.y, t.q2.z}};
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) u[j][a] = static_cast<double>(Q[j][a]) - static_cast<double>(Q[0][a]);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        e[0][a] = u[1][a] - u[0][a];
+        e[1][a] = u[2][a] - u[1][a];
+        e[2][a] = u[0][a] - u[2][a];
+    }
+}
+
+// false for an empty query: a NaN or infinite component (step 0), or n_Q exactly (0,0,0) (step 3).
+__device__ __forceinline__ bool make_qtri(V3 q0, V3 q1, V3 q2, QTri &t) {
+    t.q0 = q0;
+    t.q1 = q1;
+    t.q2 = q2;
+    t.lo = mk(fminf(fminf(q0.x, q1.x), q2.x), fminf(fminf(q0.y, q1.y), q2.y), fminf(fminf(q0.z, q1.z), q2.z));
+    t.hi = mk(fmaxf(fmaxf(q0.x, q1.x), q2.x), fmaxf(fmaxf(q0.y, q1.y), q2.y), fmaxf(fmaxf(q0.z, q1.z), q2.z));
+    if (!(inside_point_finite(q0) && inside_point_finite(q1) && inside_point_finite(q2))) return false;
+    double u[3][3], e[3][3], nq[3];
+    tri_query_edges(t, u, e);
+    cross64(e[0], e[1], nq);
+    return !(nq[0] == 0.0 && nq[1] == 0.0 && nq[2] == 0.0);
+}
+
+// Whether triangle idx is a candidate, is not passed over for the query's self triangle, and overlaps the query.
+__device__ __forceinline__ bool tri_eval(const TriQuery &q, const TriRec *__restrict__ tris, int idx, const QTri &t) {
+    const float4 nrec = reinterpret_cast<const float4 *>(tris + idx)[3];
+    if (nrec.x == 0.0f && nrec.y == 0.0f && nrec.z == 0.0f) return false;
+    const uint32_t *__restrict__ tv = q.tri_v + 3 * static_cast<size_t>(idx);
+    const uint32_t i0 = tv[0], i1 = tv[1], i2 = tv[2];
+    // self: index compares, before any vertex is loaded
+    if (t.self >= 0 && (idx == t.self || i0 == t.s0 || i0 == t.s1 || i0 == t.s2 || i1 == t.s0 || i1 == t.s1 || i1 == t.s2 || i2 == t.s0 ||
+                        i2 == t.s1 || i2 == t.s2))
+        return false;
+    const float *__restrict__ A = q.xyz + 3 * static_cast<size_t>(i0);
+    const float *__restrict__ B = q.xyz + 3 * static_cast<size_t>(i1);
+    const float *__restrict__ Cv = q.xyz + 3 * static_cast<size_t>(i2);
+    const float V[3][3] = {{A[0], A[1], A[2]}, {B[0], B[1], B[2]}, {Cv[0], Cv[1], Cv[2]}};
+    const float lo[3] = {t.lo.x, t.lo.y, t.lo.z}, hi[3] = {t.hi.x, t.hi.y, t.hi.z};
+    // 1: raw compares (most leaf triangles end here, before any binary64)
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        if (V[0][a] > hi[a] && V[1][a] > hi[a] && V[2][a] > hi[a]) return false;
+        if (V[0][a] < lo[a] && V[1][a] < lo[a] && V[2][a] < lo[a]) return false;
+    }
+    // 2, 3: binary64, relative to Q_0. (The query's side does not depend on the candidate, and the compiler hoists it
+    // out of the walk: some 40 VGPRs held across it, which is why these kernels run at two waves per SIMD. Computing it
+    // here from coordinates passed through an empty asm, so that nothing can be hoisted, gave a third wave and 12-23% on
+    // a million random queries, but cost up to 9% on the lists and up to 60% on the four-wide verdict of the two mesh sets:
+    // profiles/triangle_overlap_nohoist_ab.txt.)
+    double u[3][3], e[3][3], v[3][3], f[3][3];
+    tri_query_edges(t, u, e);
+    const float Q0[3] = {t.q0.x, t.q0.y, t.q0.z};
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) v[j][a] = static_cast<double>(V[j][a]) - static_cast<double>(Q0[a]);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        f[0][a] = v[1][a] - v[0][a];
+        f[1][a] = v[2][a] - v[1][a];
+        f[2][a] = v[0][a] - v[2][a];
+    }
+    // 4: the two normals first (they separate most pairs that pass step 1), then the nine edge pairs, then the six
+    // in-plane axes; a group that has separated ends the evaluation (the verdict is an OR over the axes)
+    double nq[3], nv[3], w[3];
+    cross64(e[0], e[1], nq);
+    cross64(f[0], f[1], nv);
+    if (tri_axis(nq, u, v) || tri_axis(nv, u, v)) return false;
+    bool sep = false;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            cross64(e[i], f[j], w);
+            sep |= tri_axis(w, u, v);
+        }
+    if (sep) return false;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        cross64(nq, e[i], w);
+        sep |= tri_axis(w, u, v);
+        cross64(nv, f[i], w);
+        sep |= tri_axis(w, u, v);
+    }
+    return !sep;
+}
+
+struct TriLeaf {
+    using Query = TriQuery;
+    using State = QTri;
+    static __device__ __forceinline__ bool eval(const TriQuery &q, const TriRec *__restrict__ tris, int idx, const QTri &t) {
+        return tri_eval(q, tris, idx, t);
+    }
+};
+
+// Vertex i (of 3n, query-major) of the query triangles in either layout; the index is 64-bit: 3n may pass 2^31.
+template <int kStride>
+__device__ __forceinline__ V3 load_tri_vertex(const void *__restrict__ a, size_t i) {
+    if (kStride == 4) {
+        const float4 v = static_cast<const float4 *>(a)[i];
+        return mk(v.x, v.y, v.z);
+    }
+    return static_cast<const V3 *>(a)[i];
+}
+
+template <int kStride>
+__device__ __forceinline__ bool load_qtri(const void *__restrict__ qt, const TriQuery &q, int j, QTri &t, int &after) {
+    after = q.after ? q.after[j] : -1;
+    const int self = q.self ? q.self[j] : -1;
+    if (self >= 0 && self < q.nt) {
+        const uint32_t *__restrict__ sv = q.tri_v + 3 * static_cast<size_t>(self);
+        t.self = self;
+        t.s0 = sv[0];
+        t.s1 = sv[1];
+        t.s2 = sv[2];
+    }
+    const size_t v0 = 3 * static_cast<size_t>(j);
+    return make_qtri(load_tri_vertex<kStride>(qt, v0), load_tri_vertex<kStride>(qt, v0 + 1), load_tri_vertex<kStride>(qt, v0 + 2), t);
+}
+
+__device__ __forceinline__ QTri no_qtri() {
+    QTri t;
+    t.lo = t.hi = t.q0 = t.q1 = t.q2 = mk(0, 0, 0);
+    t.self = -1;
+    t.s0 = t.s1 = t.s2 = 0;
+    return t;
+}
+
+template <int W, int kStride, int kMode, bool kCount>
+__global__ __launch_bounds__(kBvhBlock) void k_bvh_tri(const DevScene sc, const void *__restrict__ qt, int n,
+                                                       const int32_t *__restrict__ d_count, const TriQuery q) {
+    extern __shared__ int32_t lds_stack[];
+    const LaneStack stack = lane_stack(sc, lds_stack);
+    int32_t *const lists = lds_after_stack(sc, lds_stack);
+    WorkTally<kCount> wt;
+    drive_queries(live_rays(d_count, n), 0, nullptr, [&](int j, int end) {
+        const bool active = j < end;
+        QTri t = no_qtri();
+        int after = -1;
+        bool walk = false;
+        if (active) walk = load_qtri<kStride>(qt, q, j, t, after);
+        BoxList bl;
+        bl.idx = lists + threadIdx.x;   // (kBoxAny: never touched, and the launch has no LDS for it)
+        bl.width = kBvhBlock;
+        bl.k = kMode == kBoxAny ? 0 : q.k;
+        bool found = false;
+        wt.begin();
+        bvh_box_walk<W, kMode, TriLeaf>(sc, q, t, walk, after, bl, found, stack, wt.tests, wt.visits);
+        wt.end();
+        if (!active) return;
+        if (kMode == kBoxAny) q.collides[j] = found ? 1 : 0;
+        else store_box<kMode>(bl, j, q);
+    });
+    wt.flush(sc.work);
+}
+
+// The same over every triangle in index order (RT_ACCEL_BRUTE_FORCE, or no tree could be built).
+template <int kStride, int kMode>
+__global__ __launch_bounds__(kBlock) void k_tri(const TriRec *__restrict__ tris, int nt, const void *__restrict__ qt, int n,
+                                                const int32_t *__restrict__ d_count, const TriQuery q) {
+    extern __shared__ int32_t lds_stack[];   // the lists alone
+    int j;
+    bool active;
+    if (!brute_lane(d_count, n, j, active)) return;
+    QTri t = no_qtri();
+    int after = -1;
+    bool walk = false;
+    if (active) walk = load_qtri<kStride>(qt, q, j, t, after);
+    BoxList bl;
+    bl.idx = lds_stack + threadIdx.x;
+    bl.width = kBlock;
+    bl.k = kMode == kBoxAny ? 0 : q.k;
+    bool found = !walk;         // (kBoxAny) a lane whose query is empty has nothing to look for
+    for (int i = 0; i < nt; ++i) {
+        if (kMode == kBoxAny && (i & 15) == 0 && __all(found)) break;
+        if (walk) box_visit<kMode, TriLeaf>(q, tris, i, t, after, bl, found);
+    }
+    if (!active) return;
+    if (kMode == kBoxAny) q.collides[j] = walk && found ? 1 : 0;
     else store_box<kMode>(bl, j, q);
 }
 
@@ -5654,6 +5917,34 @@ void launch_box_occupied(const DevScene &s, const float *xyz, const uint32_t *tr
     if (n <= 0) return;
     const BoxQuery q{xyz, tri_v, hi, nullptr, 0, nullptr, nullptr, occupied};
     launch_box_mode<kBoxAny>(s, lo, box_stride, n, d_count, q, stream);
+}
+
+namespace {
+template <int kMode>
+void launch_tri_mode(const DevScene &s, const void *qtris, int32_t tri_stride, int32_t n, const int32_t *d_count, const TriQuery &q,
+                     hipStream_t stream) {
+    for_stride(tri_stride, [&](auto st) {
+        constexpr int kStride = st;
+        launch_query(s, n, kMode != kBoxAny ? box_lds(q.k) : 0, stream, [](auto w, auto c) { return k_bvh_tri<w, kStride, kMode, c>; },
+                     k_tri<kStride, kMode>, qtris, n, d_count, q);
+    });
+}
+}  // namespace
+
+void launch_tri_query(const DevScene &s, const float *xyz, const uint32_t *tri_v, bool count_all, const void *qtris, int32_t tri_stride,
+                      int32_t n, const int32_t *d_count, const int32_t *after, const int32_t *self, int32_t k, int32_t *tris_out,
+                      int32_t *nfound, hipStream_t stream) {
+    if (n <= 0) return;
+    const TriQuery q{xyz, tri_v, s.nt, after, self, k, tris_out, nfound, nullptr};
+    if (count_all) launch_tri_mode<kBoxListAll>(s, qtris, tri_stride, n, d_count, q, stream);
+    else launch_tri_mode<kBoxList>(s, qtris, tri_stride, n, d_count, q, stream);
+}
+
+void launch_tri_collides(const DevScene &s, const float *xyz, const uint32_t *tri_v, const void *qtris, int32_t tri_stride, int32_t n,
+                         const int32_t *d_count, const int32_t *self, uint8_t *collides, hipStream_t stream) {
+    if (n <= 0) return;
+    const TriQuery q{xyz, tri_v, s.nt, nullptr, self, 0, nullptr, nullptr, collides};
+    launch_tri_mode<kBoxAny>(s, qtris, tri_stride, n, d_count, q, stream);
 }
 
 namespace {
