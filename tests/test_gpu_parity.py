@@ -599,6 +599,29 @@ def test_wave_steal_auto_trials_keep_results(w, h, pf, quarter, ncand, workdir, 
         assert t["steal_quarter"] in ((0,) if quarter == 0 else (0, 64))
 
 
+@pytest.mark.parametrize("quarter,ncand", [(0, 6), (-1, 9)])
+def test_wave_steal_auto_trials_decide_at_fixed_launch(quarter, ncand, workdir, gpu_available):
+    """The launch schedule of the trials seen from outside (raytracert_amd/csrc/launch_policy.h; the host
+    check tests/test_launch_policy.py walks the same schedule): after RT_TUNE_FORGET_ORDER, launch 1 runs on
+    the cold estimate, launches 2-4 on orders of generation 0, 1, 1, launches 5 .. 5 + 2 x candidates are the
+    1 + 2 x candidates timed trials, and the launch after them reads their times. render() synchronises, so no
+    trial is still running when the next launch polls it: the choice is unset after each of the first
+    5 + 2 x candidates renders and set after the next."""
+    p = R.RenderParams(width=64, height=48, pf=1, max_lvl=1, lights=[[0, 0, 4], [1.5, 1.5, 4]])
+    with R.Scene.load(scene_path("ref:dodgeColorTest.obj", workdir), device=0) as sc:
+        sc.tune("wave_steal", 2)
+        sc.tune("chain_split", 5)
+        sc.tune("shadow_helpers", 2)
+        sc.tune("steal_quarter", quarter)
+        sc.tune("forget_order", 1)
+        for i in range(1, 6 + 2 * ncand):
+            sc.render(p)
+            assert sc.trials()["choice"] == -1, i
+        sc.render(p)
+        t = sc.trials()
+        assert t["trials"] == ncand and 0 <= t["choice"] < ncand, t
+
+
 @pytest.mark.parametrize("spec,w,h,pf,pfy,flags", [("syn:C4", 333, 187, 3, 3, 0), ("syn:F4", 96, 54, 3, 3, 0),
                                                    ("ref:dodgeColorTest.obj", 120, 90, 3, 3, 0), ("syn:F3", 70, 41, 3, 3, 1 << 8),
                                                    ("syn:F4", 17, 9, 5, 5, 0), ("syn:C4", 50, 30, 3, 5, 0),
