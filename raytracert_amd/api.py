@@ -335,30 +335,39 @@ class Scene:
         return rgb, counts
 
     # -- device-resident queries (rays and results are torch CUDA tensors; stream-ordered, no host sync) ----
-    def _device_rays(self, name: str, host_method: str, origins, dests, names=("origins", "dests")):
-        """Checks before anything touches a device: (n, ray_stride) of two CUDA float32 ray tensors."""
+    @staticmethod
+    def _instead(host_method) -> str:
+        return "there is no host method" if host_method is None else f"host arrays go through {host_method}"
+
+    def _device_rays(self, name: str, host_method, origins, dests, names=("origins", "dests"), inner: tuple = ()):
+        """Checks before anything touches a device: (n, stride) of two contiguous CUDA float32 tensors (n,) + inner +
+        (3 or 4,) of one shape on the scene's device: two ray arrays, or one tensor given twice (the points; the query
+        triangles with inner (3,)), which is then checked once."""
         import torch
-        for what, t in zip(names, (origins, dests)):
+        pair = dests is not origins
+        for what, t in zip(names, (origins, dests)) if pair else ((names[0], origins),):
             if not isinstance(t, torch.Tensor):
-                raise ValueError(f"{name}: {what} must be a CUDA torch tensor (host arrays go through {host_method})")
+                raise ValueError(f"{name}: {what} must be a CUDA torch tensor ({self._instead(host_method)})")
             if t.dtype != torch.float32:
                 raise ValueError(f"{name}: {what} must be float32, not {t.dtype}")
-            if t.dim() != 2 or t.shape[1] not in (_capi.RAYS_PACKED, _capi.RAYS_PADDED):
-                raise ValueError(f"{name}: {what} must have shape (n, 3) or (n, 4), not {tuple(t.shape)}")
+            if (t.dim() != 2 + len(inner) or t.shape[-1] not in (_capi.RAYS_PACKED, _capi.RAYS_PADDED)
+                    or (inner and t.shape[1:-1] != inner)):
+                mid = "".join(f"{m}, " for m in inner)
+                raise ValueError(f"{name}: {what} must have shape (n, {mid}3) or (n, {mid}4), not {tuple(t.shape)}")
             if not t.is_contiguous():
                 raise ValueError(f"{name}: {what} must be contiguous")
             if not t.is_cuda:
-                raise ValueError(f"{name}: {what} is a CPU tensor (host arrays go through {host_method})")
+                raise ValueError(f"{name}: {what} is a CPU tensor ({self._instead(host_method)})")
             if t.device.index != self.device:
                 raise ValueError(f"{name}: {what} is on {t.device}, the scene on device {self.device}")
-        if origins.shape != dests.shape:
+        if pair and origins.shape != dests.shape:
             raise ValueError(f"{name}: origins {tuple(origins.shape)} and dests {tuple(dests.shape)} differ in shape")
-        return int(origins.shape[0]), int(origins.shape[1])
+        return int(origins.shape[0]), int(origins.shape[-1])
 
     def _device_count(self, name: str, count):
-        import torch
         if count is None:
             return None
+        import torch
         if (not isinstance(count, torch.Tensor) or not count.is_cuda or count.dtype != torch.int32 or count.numel() != 1
                 or count.device.index != self.device):
             raise ValueError(f"{name}: count must be a CUDA int32 tensor of one element on the scene's device")
@@ -397,10 +406,9 @@ class Scene:
         name = "intersect_mesh_device"
         n, stride = self._device_rays(name, "intersect_mesh", origins, dests)
         cnt = self._device_count(name, count)
-        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
-            raise ValueError(f"{name}: out must be an (index, point) pair")
-        idx = self._device_out(name, None if out is None else out[0], n, torch.int32, (), -1, count is not None)
-        pts = self._device_out(name, None if out is None else out[1], n, torch.float32, (3,), 0.0, count is not None)
+        out_idx, out_pts = self._out_parts(name, out, 2, "out must be an (index, point) pair")
+        idx = self._device_out(name, out_idx, n, torch.int32, (), -1, count is not None)
+        pts = self._device_out(name, out_pts, n, torch.float32, (3,), 0.0, count is not None)
         check(lib().rt_intersect_mesh_device(self._h, C.c_void_p(origins.data_ptr()), C.c_void_p(dests.data_ptr()), stride, n,
                                              cnt, C.c_void_p(idx.data_ptr()), C.c_void_p(pts.data_ptr()), self._stream_ptr(stream)))
         return idx[:n], pts[:n]
@@ -418,15 +426,44 @@ class Scene:
                                        C.c_void_p(blocked.data_ptr()), self._stream_ptr(stream)))
         return blocked[:n]
 
-    def _device_bound(self, name: str, what: str, t, n: int):
-        """A ranged query's tmin / tmax: None, or a contiguous CUDA float32 tensor of n (or more) elements."""
-        import torch
+    def _device_vector(self, name: str, what: str, t, n: int, dtype):
+        """A per-query input (tmin, tmax, rmax: float32; after, self_index: int32): None, or a contiguous CUDA tensor
+        of n (or more) elements."""
         if t is None:
             return None
-        if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != self.device or t.dtype != torch.float32
+        import torch
+        if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != self.device or t.dtype != dtype
                 or t.dim() != 1 or not t.is_contiguous() or t.shape[0] < n):
-            raise ValueError(f"{name}: {what} must be a contiguous CUDA float32 tensor of shape (>= {n},) on the scene's device")
+            raise ValueError(f"{name}: {what} must be a contiguous CUDA {str(dtype).split('.')[-1]} tensor of shape (>= {n},) "
+                             f"on the scene's device")
         return C.c_void_p(t.data_ptr())
+
+    @staticmethod
+    def _list_length(name: str, k) -> None:
+        if not isinstance(k, int) or isinstance(k, bool) or k < 1 or k > _capi.MULTI_HIT_MAX:
+            raise ValueError(f"{name}: k must be an int in [1, {_capi.MULTI_HIT_MAX}], not {k!r}")
+
+    @staticmethod
+    def _out_parts(name: str, out, m: int, must: str) -> tuple:
+        """`out` as its m parts (None each without it). must: what it has to be, in the method's words."""
+        if out is None:
+            return (None,) * m
+        if not isinstance(out, (tuple, list)) or len(out) != m:
+            raise ValueError(f"{name}: {must}")
+        return tuple(out)
+
+    def _device_records(self, name: str, out, n: int, tail: tuple, fill: bool):
+        """The rt_hit record tensor, (n,) + tail int32 with tail (4,) or (k, 4): `out` checked or a new one, 16-byte
+        aligned. fill: a device count may leave entries unwritten, which then hold the miss record. Returns it with
+        the (triangle, distance, st) views of its first n records."""
+        import torch
+        rec = self._device_out(name, out, n, torch.int32, tail, 0, False)
+        if fill:
+            rec[..., 0], rec[..., 1], rec[..., 2:] = -1, 0x7F800000, 0      # (device fills: no host copy)
+        if rec.data_ptr() % _capi.HIT_BYTES:
+            raise ValueError(f"{name}: the record tensor must be 16-byte aligned")
+        f = rec[:n].view(torch.float32)
+        return rec, (rec[:n, ..., 0], f[..., 1], f[..., 2:4])
 
     def closest_hit_device(self, origins, dests, tmin=None, tmax=None, to_dest: bool = False, count=None, out=None,
                            want_points: bool = False, stream=None):
@@ -444,21 +481,13 @@ class Scene:
         name = "closest_hit_device"
         n, stride = self._device_rays(name, "intersect_mesh", origins, dests)
         cnt = self._device_count(name, count)
-        lo, hi = self._device_bound(name, "tmin", tmin, n), self._device_bound(name, "tmax", tmax, n)
-        if want_points and out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
-            raise ValueError(f"{name}: with want_points, out must be a (records, points) pair")
-        out_rec = out[0] if (want_points and out is not None) else out
-        rec = self._device_out(name, out_rec, n, torch.int32, (4,), 0, False)
-        if out_rec is None and count is not None:      # entries a device count leaves unwritten: the miss record
-            rec[:, 0], rec[:, 1], rec[:, 2:] = -1, 0x7F800000, 0      # (device fills: no host copy)
-        if rec.data_ptr() % _capi.HIT_BYTES:
-            raise ValueError(f"{name}: the record tensor must be 16-byte aligned")
-        pts = self._device_out(name, None if out is None else out[1], n, torch.float32, (3,), 0.0, count is not None) if want_points else None
+        lo, hi = self._device_vector(name, "tmin", tmin, n, torch.float32), self._device_vector(name, "tmax", tmax, n, torch.float32)
+        out_rec, out_pts = self._out_parts(name, out, 2, "with want_points, out must be a (records, points) pair") if want_points else (out, None)
+        rec, res = self._device_records(name, out_rec, n, (4,), out_rec is None and count is not None)
+        pts = self._device_out(name, out_pts, n, torch.float32, (3,), 0.0, count is not None) if want_points else None
         check(lib().rt_closest_hit_range_device(self._h, C.c_void_p(origins.data_ptr()), C.c_void_p(dests.data_ptr()), stride, n, cnt,
                                                 lo, hi, _capi.RANGE_TO_DEST if to_dest else 0, C.c_void_p(rec.data_ptr()),
                                                 None if pts is None else C.c_void_p(pts.data_ptr()), self._stream_ptr(stream)))
-        f = rec[:n].view(torch.float32)
-        res = (rec[:n, 0], f[:, 1], f[:, 2:4])
         return res + (pts[:n],) if want_points else res
 
     def multi_hit_device(self, origins, dests, k: int, tmin=None, tmax=None, to_dest: bool = False, count_all: bool = False,
@@ -472,25 +501,18 @@ class Scene:
         lowest index first. out: a (records, nhits) pair to write into, (>= n, k, 4) int32 and (>= n,) int32."""
         import torch
         name = "multi_hit_device"
-        if not isinstance(k, int) or isinstance(k, bool) or k < 1 or k > _capi.MULTI_HIT_MAX:
-            raise ValueError(f"{name}: k must be an int in [1, {_capi.MULTI_HIT_MAX}], not {k!r}")
+        self._list_length(name, k)
         n, stride = self._device_rays(name, "intersect_mesh", origins, dests)
         cnt = self._device_count(name, count)
-        lo, hi = self._device_bound(name, "tmin", tmin, n), self._device_bound(name, "tmax", tmax, n)
-        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
-            raise ValueError(f"{name}: out must be a (records, nhits) pair")
-        rec = self._device_out(name, None if out is None else out[0], n, torch.int32, (k, 4), 0, False)
-        if out is None and count is not None:          # entries a device count leaves unwritten: the miss record
-            rec[..., 0], rec[..., 1], rec[..., 2:] = -1, 0x7F800000, 0      # (device fills: no host copy)
-        if rec.data_ptr() % _capi.HIT_BYTES:
-            raise ValueError(f"{name}: the record tensor must be 16-byte aligned")
-        nh = self._device_out(name, None if out is None else out[1], n, torch.int32, (), 0, count is not None)
+        lo, hi = self._device_vector(name, "tmin", tmin, n, torch.float32), self._device_vector(name, "tmax", tmax, n, torch.float32)
+        out_rec, out_nh = self._out_parts(name, out, 2, "out must be a (records, nhits) pair")
+        rec, res = self._device_records(name, out_rec, n, (k, 4), out is None and count is not None)
+        nh = self._device_out(name, out_nh, n, torch.int32, (), 0, count is not None)
         flags = (_capi.RANGE_TO_DEST if to_dest else 0) | (_capi.MULTI_COUNT_ALL if count_all else 0)
         check(lib().rt_multi_hit_range_device(self._h, C.c_void_p(origins.data_ptr()), C.c_void_p(dests.data_ptr()), stride, n, cnt,
                                               lo, hi, flags, k, C.c_void_p(rec.data_ptr()), C.c_void_p(nh.data_ptr()),
                                               self._stream_ptr(stream)))
-        f = rec[:n].view(torch.float32)
-        return rec[:n, :, 0], f[:, :, 1], f[:, :, 2:4], nh[:n]
+        return res + (nh[:n],)
 
     def closest_point_device(self, points, rmax=None, count=None, out=None, want_points: bool = False, stream=None):
         """rt_closest_point_device: per query point, the nearest point of the mesh (include/raytracert.h states the
@@ -504,20 +526,12 @@ class Scene:
         name = "closest_point_device"
         n, stride = self._device_rays(name, "closest_point", points, points, ("points", "points"))
         cnt = self._device_count(name, count)
-        rad = self._device_bound(name, "rmax", rmax, n)
-        if want_points and out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
-            raise ValueError(f"{name}: with want_points, out must be a (records, points) pair")
-        out_rec = out[0] if (want_points and out is not None) else out
-        rec = self._device_out(name, out_rec, n, torch.int32, (4,), 0, False)
-        if out_rec is None and count is not None:      # entries a device count leaves unwritten: the miss record
-            rec[:, 0], rec[:, 1], rec[:, 2:] = -1, 0x7F800000, 0      # (device fills: no host copy)
-        if rec.data_ptr() % _capi.HIT_BYTES:
-            raise ValueError(f"{name}: the record tensor must be 16-byte aligned")
-        pts = self._device_out(name, None if out is None else out[1], n, torch.float32, (3,), 0.0, count is not None) if want_points else None
+        rad = self._device_vector(name, "rmax", rmax, n, torch.float32)
+        out_rec, out_pts = self._out_parts(name, out, 2, "with want_points, out must be a (records, points) pair") if want_points else (out, None)
+        rec, res = self._device_records(name, out_rec, n, (4,), out_rec is None and count is not None)
+        pts = self._device_out(name, out_pts, n, torch.float32, (3,), 0.0, count is not None) if want_points else None
         check(lib().rt_closest_point_device(self._h, C.c_void_p(points.data_ptr()), stride, n, cnt, rad, 0, C.c_void_p(rec.data_ptr()),
                                             None if pts is None else C.c_void_p(pts.data_ptr()), self._stream_ptr(stream)))
-        f = rec[:n].view(torch.float32)
-        res = (rec[:n, 0], f[:, 1], f[:, 2:4])
         return res + (pts[:n],) if want_points else res
 
     def nearest_triangles_device(self, points, k: int, rmax=None, count_all: bool = False, count=None, out=None,
@@ -533,27 +547,19 @@ class Scene:
         int32, or with want_points a (records, nfound, points) triple with (>= n, k, 3) float32."""
         import torch
         name = "nearest_triangles_device"
-        if not isinstance(k, int) or isinstance(k, bool) or k < 1 or k > _capi.MULTI_HIT_MAX:
-            raise ValueError(f"{name}: k must be an int in [1, {_capi.MULTI_HIT_MAX}], not {k!r}")
+        self._list_length(name, k)
         n, stride = self._device_rays(name, "closest_point", points, points, ("points", "points"))
         cnt = self._device_count(name, count)
-        rad = self._device_bound(name, "rmax", rmax, n)
-        parts = 3 if want_points else 2
-        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != parts):
-            raise ValueError(f"{name}: out must be a (records, nfound{', points' if want_points else ''}) tuple")
-        rec = self._device_out(name, None if out is None else out[0], n, torch.int32, (k, 4), 0, False)
-        if out is None and count is not None:          # entries a device count leaves unwritten: the miss record
-            rec[..., 0], rec[..., 1], rec[..., 2:] = -1, 0x7F800000, 0      # (device fills: no host copy)
-        if rec.data_ptr() % _capi.HIT_BYTES:
-            raise ValueError(f"{name}: the record tensor must be 16-byte aligned")
-        nf = self._device_out(name, None if out is None else out[1], n, torch.int32, (), 0, count is not None)
-        pts = self._device_out(name, None if out is None else out[2], n, torch.float32, (k, 3), 0.0, count is not None) if want_points else None
+        rad = self._device_vector(name, "rmax", rmax, n, torch.float32)
+        parts = self._out_parts(name, out, 3 if want_points else 2, f"out must be a (records, nfound{', points' if want_points else ''}) tuple")
+        rec, res = self._device_records(name, parts[0], n, (k, 4), out is None and count is not None)
+        nf = self._device_out(name, parts[1], n, torch.int32, (), 0, count is not None)
+        pts = self._device_out(name, parts[2], n, torch.float32, (k, 3), 0.0, count is not None) if want_points else None
         check(lib().rt_nearest_triangles_device(self._h, C.c_void_p(points.data_ptr()), stride, n, cnt, rad,
                                                 _capi.NEAR_COUNT_ALL if count_all else 0, k, C.c_void_p(rec.data_ptr()),
                                                 C.c_void_p(nf.data_ptr()), None if pts is None else C.c_void_p(pts.data_ptr()),
                                                 self._stream_ptr(stream)))
-        f = rec[:n].view(torch.float32)
-        res = (rec[:n, :, 0], f[:, :, 1], f[:, :, 2:4], nf[:n])
+        res += (nf[:n],)
         return res + (pts[:n],) if want_points else res
 
     def within_radius_device(self, points, rmax=None, count=None, out=None, stream=None):
@@ -565,7 +571,7 @@ class Scene:
         name = "within_radius_device"
         n, stride = self._device_rays(name, "closest_point", points, points, ("points", "points"))
         cnt = self._device_count(name, count)
-        rad = self._device_bound(name, "rmax", rmax, n)
+        rad = self._device_vector(name, "rmax", rmax, n, torch.float32)
         within = self._device_out(name, out, n, torch.uint8, (), 0, count is not None)
         check(lib().rt_within_radius_device(self._h, C.c_void_p(points.data_ptr()), stride, n, cnt, rad, 0,
                                             C.c_void_p(within.data_ptr()), self._stream_ptr(stream)))
@@ -588,11 +594,9 @@ class Scene:
         axis = self._inside_axis(name, axis)
         n, stride = self._device_rays(name, "closest_point", points, points, ("points", "points"))
         cnt = self._device_count(name, count)
-        if crossings and out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
-            raise ValueError(f"{name}: with crossings, out must be an (inside, crossings) pair")
-        out_in = out[0] if (crossings and out is not None) else out
+        out_in, out_cr = self._out_parts(name, out, 2, "with crossings, out must be an (inside, crossings) pair") if crossings else (out, None)
         inside = self._device_out(name, out_in, n, torch.uint8, (), 0, count is not None)
-        cr = self._device_out(name, None if out is None else out[1], n, torch.int32, (), 0, count is not None) if crossings else None
+        cr = self._device_out(name, out_cr, n, torch.int32, (), 0, count is not None) if crossings else None
         check(lib().rt_point_inside_device(self._h, C.c_void_p(points.data_ptr()), stride, n, cnt, axis, 0,
                                            C.c_void_p(inside.data_ptr()), None if cr is None else C.c_void_p(cr.data_ptr()),
                                            self._stream_ptr(stream)))
@@ -610,22 +614,15 @@ class Scene:
         axis = self._inside_axis(name, axis)
         n, stride = self._device_rays(name, "closest_point", points, points, ("points", "points"))
         cnt = self._device_count(name, count)
-        rad = self._device_bound(name, "rmax", rmax, n)
-        if want_points and out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
-            raise ValueError(f"{name}: with want_points, out must be a (records, points) pair")
-        out_rec = out[0] if (want_points and out is not None) else out
-        rec = self._device_out(name, out_rec, n, torch.int32, (4,), 0, False)
-        if out_rec is None and count is not None:      # entries a device count leaves unwritten: the miss record
-            rec[:, 0], rec[:, 1], rec[:, 2:] = -1, 0x7F800000, 0      # (device fills: no host copy)
-        if rec.data_ptr() % _capi.HIT_BYTES:
-            raise ValueError(f"{name}: the record tensor must be 16-byte aligned")
-        pts = self._device_out(name, None if out is None else out[1], n, torch.float32, (3,), 0.0, count is not None) if want_points else None
+        rad = self._device_vector(name, "rmax", rmax, n, torch.float32)
+        out_rec, out_pts = self._out_parts(name, out, 2, "with want_points, out must be a (records, points) pair") if want_points else (out, None)
+        rec, res = self._device_records(name, out_rec, n, (4,), out_rec is None and count is not None)
+        pts = self._device_out(name, out_pts, n, torch.float32, (3,), 0.0, count is not None) if want_points else None
         inside = self._device_out(name, None, n, torch.uint8, (), 0, count is not None)
         check(lib().rt_signed_distance_device(self._h, C.c_void_p(points.data_ptr()), stride, n, cnt, rad, axis, 0,
                                               C.c_void_p(rec.data_ptr()), None if pts is None else C.c_void_p(pts.data_ptr()),
                                               C.c_void_p(inside.data_ptr()), self._stream_ptr(stream)))
-        f = rec[:n].view(torch.float32)
-        res = (rec[:n, 0], f[:, 1], f[:, 2:4], inside[:n])
+        res += (inside[:n],)
         return res + (pts[:n],) if want_points else res
 
     def box_overlap_device(self, lo, hi, k: int, after=None, count=None, count_all: bool = False, out=None, stream=None):
@@ -640,20 +637,15 @@ class Scene:
         into, (>= n, k) int32 and (>= n,) int32; the result is then views of them."""
         import torch
         name = "box_overlap_device"
-        if not isinstance(k, int) or isinstance(k, bool) or k < 1 or k > _capi.MULTI_HIT_MAX:
-            raise ValueError(f"{name}: k must be an int in [1, {_capi.MULTI_HIT_MAX}], not {k!r}")
+        self._list_length(name, k)
         n, stride = self._device_rays(name, "no host method", lo, hi, ("lo", "hi"))
         cnt = self._device_count(name, count)
-        if after is not None and (not isinstance(after, torch.Tensor) or not after.is_cuda or after.device.index != self.device
-                                  or after.dtype != torch.int32 or after.dim() != 1 or not after.is_contiguous() or after.shape[0] < n):
-            raise ValueError(f"{name}: after must be a contiguous CUDA int32 tensor of shape (>= {n},) on the scene's device")
-        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
-            raise ValueError(f"{name}: out must be a (tris, nfound) pair")
-        tris = self._device_out(name, None if out is None else out[0], n, torch.int32, (k,), -1, count is not None)
-        nf = self._device_out(name, None if out is None else out[1], n, torch.int32, (), 0, count is not None)
+        aft = self._device_vector(name, "after", after, n, torch.int32)
+        out_tris, out_nf = self._out_parts(name, out, 2, "out must be a (tris, nfound) pair")
+        tris = self._device_out(name, out_tris, n, torch.int32, (k,), -1, count is not None)
+        nf = self._device_out(name, out_nf, n, torch.int32, (), 0, count is not None)
         check(lib().rt_box_overlap_device(self._h, C.c_void_p(lo.data_ptr()), C.c_void_p(hi.data_ptr()), stride, n, cnt,
-                                          None if after is None else C.c_void_p(after.data_ptr()),
-                                          _capi.BOX_COUNT_ALL if count_all else 0, k, C.c_void_p(tris.data_ptr()),
+                                          aft, _capi.BOX_COUNT_ALL if count_all else 0, k, C.c_void_p(tris.data_ptr()),
                                           C.c_void_p(nf.data_ptr()), self._stream_ptr(stream)))
         return tris[:n], nf[:n]
 
@@ -672,30 +664,7 @@ class Scene:
 
     def _device_tris(self, name: str, tris):
         """Checks before anything touches a device: (n, tri_stride) of a CUDA float32 tensor of query triangles."""
-        import torch
-        if not isinstance(tris, torch.Tensor):
-            raise ValueError(f"{name}: tris must be a CUDA torch tensor (there is no host method)")
-        if tris.dtype != torch.float32:
-            raise ValueError(f"{name}: tris must be float32, not {tris.dtype}")
-        if tris.dim() != 3 or tris.shape[1] != 3 or tris.shape[2] not in (_capi.RAYS_PACKED, _capi.RAYS_PADDED):
-            raise ValueError(f"{name}: tris must have shape (n, 3, 3) or (n, 3, 4), not {tuple(tris.shape)}")
-        if not tris.is_contiguous():
-            raise ValueError(f"{name}: tris must be contiguous")
-        if not tris.is_cuda:
-            raise ValueError(f"{name}: tris is a CPU tensor (there is no host method)")
-        if tris.device.index != self.device:
-            raise ValueError(f"{name}: tris is on {tris.device}, the scene on device {self.device}")
-        return int(tris.shape[0]), int(tris.shape[2])
-
-    def _device_index(self, name: str, what: str, t, n: int):
-        """A per-query index array (after, self_index): None, or a contiguous CUDA int32 tensor of n (or more) elements."""
-        import torch
-        if t is None:
-            return None
-        if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != self.device or t.dtype != torch.int32
-                or t.dim() != 1 or not t.is_contiguous() or t.shape[0] < n):
-            raise ValueError(f"{name}: {what} must be a contiguous CUDA int32 tensor of shape (>= {n},) on the scene's device")
-        return C.c_void_p(t.data_ptr())
+        return self._device_rays(name, None, tris, tris, ("tris", "tris"), (3,))
 
     def triangle_overlap_device(self, tris, k: int, after=None, self_index=None, count=None, count_all: bool = False, out=None,
                                 stream=None):
@@ -713,16 +682,14 @@ class Scene:
         (>= n, k) int32 and (>= n,) int32; the result is then views of them."""
         import torch
         name = "triangle_overlap_device"
-        if not isinstance(k, int) or isinstance(k, bool) or k < 1 or k > _capi.MULTI_HIT_MAX:
-            raise ValueError(f"{name}: k must be an int in [1, {_capi.MULTI_HIT_MAX}], not {k!r}")
+        self._list_length(name, k)
         n, stride = self._device_tris(name, tris)
         cnt = self._device_count(name, count)
-        aft = self._device_index(name, "after", after, n)
-        slf = self._device_index(name, "self_index", self_index, n)
-        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
-            raise ValueError(f"{name}: out must be a (tris, nfound) pair")
-        found = self._device_out(name, None if out is None else out[0], n, torch.int32, (k,), -1, count is not None)
-        nf = self._device_out(name, None if out is None else out[1], n, torch.int32, (), 0, count is not None)
+        aft = self._device_vector(name, "after", after, n, torch.int32)
+        slf = self._device_vector(name, "self_index", self_index, n, torch.int32)
+        out_tris, out_nf = self._out_parts(name, out, 2, "out must be a (tris, nfound) pair")
+        found = self._device_out(name, out_tris, n, torch.int32, (k,), -1, count is not None)
+        nf = self._device_out(name, out_nf, n, torch.int32, (), 0, count is not None)
         check(lib().rt_triangle_overlap_device(self._h, C.c_void_p(tris.data_ptr()), stride, n, cnt, aft, slf,
                                                _capi.TRI_COUNT_ALL if count_all else 0, k, C.c_void_p(found.data_ptr()),
                                                C.c_void_p(nf.data_ptr()), self._stream_ptr(stream)))
@@ -737,7 +704,7 @@ class Scene:
         name = "triangle_collides_device"
         n, stride = self._device_tris(name, tris)
         cnt = self._device_count(name, count)
-        slf = self._device_index(name, "self_index", self_index, n)
+        slf = self._device_vector(name, "self_index", self_index, n, torch.int32)
         col = self._device_out(name, out, n, torch.uint8, (), 0, count is not None)
         check(lib().rt_triangle_collides_device(self._h, C.c_void_p(tris.data_ptr()), stride, n, cnt, slf, 0,
                                                 C.c_void_p(col.data_ptr()), self._stream_ptr(stream)))
@@ -769,7 +736,7 @@ class Scene:
         name = "occluded_range_device"
         n, stride = self._device_rays(name, "intersect_mesh", origins, dests)
         cnt = self._device_count(name, count)
-        lo, hi = self._device_bound(name, "tmin", tmin, n), self._device_bound(name, "tmax", tmax, n)
+        lo, hi = self._device_vector(name, "tmin", tmin, n, torch.float32), self._device_vector(name, "tmax", tmax, n, torch.float32)
         blocked = self._device_out(name, out, n, torch.uint8, (), 0, count is not None)
         flags = (_capi.RANGE_TO_DEST if to_dest else 0) | (_capi.OCCLUDE_ANY_OPAQUE if any_opaque else 0)
         check(lib().rt_occluded_range_device(self._h, C.c_void_p(origins.data_ptr()), C.c_void_p(dests.data_ptr()), stride, n, cnt,

@@ -192,16 +192,25 @@ def test_multiframe_and_reserve_entries_refuse_without_a_device(tmp_path):
 
 def test_every_c_entry_is_exception_guarded():
     """No C++ exception crosses the C ABI (a failed host allocation is RT_E_NOMEM, not std::terminate in
-    the host): every rt_* entry defined in the library's C-ABI sources runs its body in try/catch."""
+    the host): every rt_* entry defined in the library's C-ABI sources runs its body in try/catch, its own or
+    device_entry's (the device-resident entries' shared guard: their whole body is the one call of it)."""
     import os
     import re
     src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "raytracert_amd", "csrc")
-    seen = 0
+    seen = shared = 0
     for f in ("rt_capi.cpp", "rt_comm.cpp"):
         text = open(os.path.join(src, f)).read()
-        for m in re.finditer(r"^(int|void) (rt_\w+)\([^;{]*\)\s*\{\n(\s*)(\S+)", text, re.M):
+        for m in re.finditer(r"^(int|void) (rt_\w+)\([^;{]*\)\s*\{\n(\s*)([^\n]+)", text, re.M):
             seen += 1
-            assert m.group(4) == "try", f"{f}: {m.group(2)} is not wrapped in try/catch"
             body = text[m.end():text.find("\n}\n", m.end())]
+            if m.group(4).startswith("return device_entry(s, [&]"):
+                shared += 1
+                assert body.endswith("\n    });"), f"{f}: {m.group(2)} has statements outside device_entry"
+                continue
+            assert m.group(4).split()[0] == "try", f"{f}: {m.group(2)} is not wrapped in try/catch"
             assert "catch (...)" in body, f"{f}: {m.group(2)} has no catch (...)"
-    assert seen >= 50
+        if f == "rt_capi.cpp":
+            g = re.search(r"^static int device_entry\([^;{]*\)\s*\{\n(\s*)(\S+)", text, re.M)
+            assert g and g.group(2) == "try", "device_entry does not run the body in try/catch"
+            assert "catch (...)" in text[g.end():text.find("\n}\n", g.end())], "device_entry has no catch (...)"
+    assert seen >= 50 and shared >= 15
