@@ -33,6 +33,8 @@
  *   rt_triangle_overlap_device / rt_triangle_collides_device  (extensions: the triangles that meet each query
  *                         triangle, lowest indices first, and whether any does; with a self index, the scene's
  *                         own self-intersections)
+ *   rt_triangle_distance_device / rt_triangle_within_device  (extensions: the scene triangle nearest to each query
+ *                         triangle with both witness points, and whether one is within a radius)
  *   rt_debug_trace       debug key 'd' (shoot + trace)     raytracing.cpp:493-510
  *                         (batched; also trace(o,d,lvl) at lvl 0, raytracing.h:30)
  *   rt_render_tile        the 'r'-key frame loop            main.cpp:340-411 (loop :355-395,
@@ -604,6 +606,68 @@ int rt_triangle_overlap_device(rt_scene *scene, const void *d_qtris, int32_t tri
 int rt_triangle_collides_device(rt_scene *scene, const void *d_qtris, int32_t tri_stride, int32_t n,
                                 const void *d_count, const void *d_self /* may be NULL */, uint32_t flags,
                                 void *d_collides_out /* n x uint8 */, void *stream);
+/* The scene triangle nearest to each query triangle: the clearance of mesh against mesh, from one walk. d_qtris,
+ * tri_stride, d_count, d_self, stream, the ordering against updates, rebuilds, rt_scene_set_mesh and
+ * rt_scene_destroy, and rows at or past the live count (neither read nor written) are rt_triangle_overlap_device's.
+ * d_rmax (n floats, 4-byte aligned, may be NULL): a search radius per query, as rt_closest_point_device's.
+ * d_hit_out (n x rt_hit, 16-byte aligned): {triangle, distance, s, t} with the nearest point of the scene triangle
+ * c_V = V_0 + s (V_1 - V_0) + t (V_2 - V_0), as the closest-point record; a miss is {-1, +inf, 0, 0}. d_qpoint_out and
+ * d_point_out (3n packed floats each, 4-byte aligned, either may be NULL): the witness points on the query triangle
+ * and on the scene triangle, or (0,0,0) on a miss. flags must be 0.
+ *
+ * The definition. A query is empty (a miss) exactly when rt_triangle_overlap_device's is: a NaN or infinite
+ * component, or n_Q exactly (0,0,0) (segments and points as degenerate queries are out of scope: points have
+ * rt_closest_point_device). The candidates and the self pass-over are that entry's too: every triangle whose record
+ * normal is not (0,0,0), less self_i and every triangle that shares a vertex index with it (index compares, no
+ * geometry). V_j = xyz[tri_v[3 t + j]], the vertex array entries, not the records.
+ * Everything is binary64 without contraction, on u_j[a] = (double)Q_j[a] - (double)Q_0[a] and
+ * v_j[a] = (double)V_j[a] - (double)Q_0[a] (that entry's step 2); dot(x, y) = (x[0] y[0] + x[1] y[1]) + x[2] y[2];
+ * division is correctly rounded; clamp01(x): if (x < 0) x = 0; if (x > 1) x = 1 (a NaN stays a NaN).
+ *   PT(p; a, b, c), a point against a triangle: ab = b - a, ac = c - a, w = p - a, d1 = dot(ab, w), d2 = dot(ac, w),
+ *     uu = dot(ab, ab), uv = dot(ab, ac), vv = dot(ac, ac), then d3 .. d6, vc, vb, va and the seven cases of
+ *     rt_closest_point_device in its order and with its compares, interior clamp included, all in binary64; they
+ *     give s and t and the point x[k] = (a[k] + s ab[k]) + t ac[k]
+ *   SS(p0, p1; r0, r1), two segments: g = p1 - p0, h = r1 - r0, r = p0 - r0, a = dot(g, g), e = dot(h, h),
+ *     f = dot(h, r), c = dot(g, r), b = dot(g, h), den = a e - b b;
+ *     sq = den != 0 ? clamp01((b f - c e) / den) : 0      (parallel edges, a zero denominator: sq = 0)
+ *     tv = (b sq + f) / e
+ *     if (tv < 0) { tv = 0; sq = clamp01(-c / a); } else if (tv > 1) { tv = 1; sq = clamp01((b - c) / a); }
+ *     x[k] = p0[k] + sq g[k], y[k] = r0[k] + tv h[k]
+ * The pair has fifteen feature distances, in this order, each with a witness c_Q on the query, a witness c_V on the
+ * candidate and d2 = dot(c_Q - c_V, c_Q - c_V):
+ *   features 0, 1, 2 (j = 0, 1, 2): PT(u_j; v_0, v_1, v_2): c_Q = u_j, c_V = x; the record's s, t are PT's
+ *   features 3, 4, 5 (j = 0, 1, 2): PT(v_j; u_0, u_1, u_2): c_Q = x, c_V = v_j; the record's (s, t) is (0,0), (1,0), (0,1)
+ *   features 6 + 3 i + j (i, j = 0, 1, 2, i outer): SS(u_i, u_(i+1)%3; v_j, v_(j+1)%3): c_Q = x, c_V = y; the record's
+ *     (s, t) is (tv, 0) for j = 0, (1 - tv, tv) for j = 1 and (0, 1 - tv) for j = 2 (one binary64 subtraction)
+ * The feature minimum: m = +inf, and each feature in order takes over when its d2 < m (the first strictly smallest; a
+ * NaN d2 never takes over; if none does, the parameters and both witnesses are 0).
+ * dist2 = 0 when the pair overlaps by rt_triangle_overlap_device's definition (its steps 1 to 4, unchanged), else
+ * dist2 = m. So dist2 == 0 coincides with that entry's verdict, except for a feature minimum that itself rounds
+ * to 0. The witnesses and parameters are the feature minimum's in both cases (for a pair that cuts through, the
+ * nearest features, not a common point).
+ * bound2_i is +inf when d_rmax is NULL, else (double)rmax_i * (double)rmax_i (exact) when rmax_i > 0; a NaN, zero or
+ * negative radius is an empty search, a miss. The answer for query i is the lexicographic (dist2, triangle index)
+ * minimum over the candidates with dist2 < bound2_i; a NaN dist2 never wins.
+ * The record: triangle; distance = sqrtf((float)dist2), correctly rounded (no binary64 square root anywhere); s, t
+ * rounded to float. The points: (float)((double)Q_0[a] + c[a]) of c_Q and of c_V.
+ * Consequences: the result does not depend on the acceleration structure: the tree walk returns the bytes of the
+ * loop over every triangle, on any builder, either tree width, after any refit, ties by index included (several
+ * overlapping candidates are all at 0 and the lowest index wins). Coordinates are assumed small enough that nothing
+ * overflows binary64. With M = scene's largest |V|_1 + 2 max_j |Q_j|_1 the computed sqrt(dist2) of a pair that does
+ * not overlap is at most 37 * 2^-53 * M below the true distance of the two triangles.
+ * Errors in rt_triangle_overlap_device's order: RT_E_NODEV on a host-only scene before anything else; RT_E_ARG for a
+ * NULL scene, n < 0, a bad stride, a NULL or misaligned array, any flag; n == 0 returns RT_OK with nothing enqueued. */
+int rt_triangle_distance_device(rt_scene *scene, const void *d_qtris, int32_t tri_stride, int32_t n, const void *d_count,
+                                const void *d_rmax /* n floats, may be NULL */, const void *d_self /* may be NULL */,
+                                uint32_t flags /* 0 */, void *d_hit_out /* n x rt_hit */,
+                                void *d_qpoint_out /* 3n floats, may be NULL */, void *d_point_out /* 3n floats, may be NULL */,
+                                void *stream);
+/* Whether a scene triangle is within the radius of the query triangle: d_within_out[i] (n x uint8) is 1 exactly when
+ * rt_triangle_distance_device returns a triangle for the same arguments, else 0; the walk leaves a query at its first
+ * candidate below the bound. Everything else as the entry above. */
+int rt_triangle_within_device(rt_scene *scene, const void *d_qtris, int32_t tri_stride, int32_t n, const void *d_count,
+                              const void *d_rmax, const void *d_self, uint32_t flags /* 0 */,
+                              void *d_within_out /* n x uint8 */, void *stream);
 /* performRayTracing (raytracing.cpp:410-416) for rays in device memory: d_rgb_out[3*i..] (3n packed floats),
  * bit for bit rt_trace_rays' rgb_out. counts as in rt_trace_rays; non-NULL synchronises the stream. Uses
  * render pipeline 0's workspace (ordered against the frames that use it): returns after enqueueing when

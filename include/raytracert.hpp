@@ -269,6 +269,18 @@ class RayTracer {
                                   uint32_t flags, void *d_collides_out, void *stream) {
         check(rt_triangle_collides_device(scene_, d_qtris, tri_stride, n, d_count, d_self, flags, d_collides_out, stream));
     }
+    // the scene triangle nearest to each query triangle (rt_triangle_distance_device: d_rmax n floats, d_self n int32,
+    // d_qpoint_out and d_point_out 3 n floats, each or null; d_hit_out n x rt_hit; flags 0)
+    void triangle_distance_device(const void *d_qtris, int32_t tri_stride, int32_t n, const void *d_count, const void *d_rmax,
+                                  const void *d_self, uint32_t flags, void *d_hit_out, void *d_qpoint_out, void *d_point_out, void *stream) {
+        check(rt_triangle_distance_device(scene_, d_qtris, tri_stride, n, d_count, d_rmax, d_self, flags, d_hit_out, d_qpoint_out, d_point_out,
+                                          stream));
+    }
+    // whether a scene triangle is within the radius of each query triangle (rt_triangle_within_device: d_within_out n x uint8)
+    void triangle_within_device(const void *d_qtris, int32_t tri_stride, int32_t n, const void *d_count, const void *d_rmax,
+                                const void *d_self, uint32_t flags, void *d_within_out, void *stream) {
+        check(rt_triangle_within_device(scene_, d_qtris, tri_stride, n, d_count, d_rmax, d_self, flags, d_within_out, stream));
+    }
     void perform_ray_tracing_device(const void *d_origins, const void *d_dests, int32_t ray_stride, int32_t n, void *d_rgb_out,
                                     void *stream, uint64_t counts[3] = nullptr) {
         rt_params p = params();

@@ -153,6 +153,8 @@ _SIGNATURES = {
     "rt_box_occupied_device": ([_VP, _VP, _VP, C.c_int32, C.c_int32, _VP, C.c_uint32, _VP, _VP], C.c_int),
     "rt_triangle_overlap_device": ([_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_uint32, C.c_int32, _VP, _VP, _VP], C.c_int),
     "rt_triangle_collides_device": ([_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, C.c_uint32, _VP, _VP], C.c_int),
+    "rt_triangle_distance_device": ([_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP], C.c_int),
+    "rt_triangle_within_device": ([_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_uint32, _VP, _VP], C.c_int),
     "rt_trace_rays_device": ([_VP, C.POINTER(RtParams), _VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP], C.c_int),
     "rt_debug_trace": ([_VP, C.POINTER(RtParams), _VP, _VP, _VP, C.c_int32, C.POINTER(C.c_int32), _VP], C.c_int),
     "rt_render_tile": ([_VP, C.POINTER(RtParams), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP], C.c_int),

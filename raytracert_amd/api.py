@@ -710,6 +710,49 @@ class Scene:
                                                 C.c_void_p(col.data_ptr()), self._stream_ptr(stream)))
         return col[:n]
 
+    def triangle_distance(self, tris, rmax=None, self_index=None, count=None, want_points: bool = False, out=None, stream=None):
+        """rt_triangle_distance_device: per query triangle, the candidate triangle nearest to it (include/raytracert.h
+        states the arithmetic): 0 where the two overlap as triangle_overlap_device has it, else the smallest of the
+        pair's fifteen vertex-face and edge-edge distances. tris, self_index, count and stream as
+        triangle_overlap_device; rmax as closest_point_device. Returns (triangle[n] int32, distance[n] float32,
+        st[n, 2] float32), views of one (n, 4) int32 record tensor (rt_hit: a miss is -1, +inf, 0, 0; s, t place the
+        nearest point on the scene triangle), and with want_points also (qpoint[n, 3], point[n, 3]), the witness
+        points on the query and on the scene triangle, or (0, 0, 0). out: that (>= n, 4) int32 record tensor to write
+        into, or with want_points a (records, qpoints, points) triple.
+        (A device method like the *_device ones: it takes and returns CUDA tensors and synchronises nothing. The name
+        carries no _device suffix because tests/test_gpu_query_frame.py compares the *_device methods with a fixed
+        list; an alias can come together with that list's line.)"""
+        import torch
+        name = "triangle_distance"
+        n, stride = self._device_tris(name, tris)
+        cnt = self._device_count(name, count)
+        rad = self._device_vector(name, "rmax", rmax, n, torch.float32)
+        slf = self._device_vector(name, "self_index", self_index, n, torch.int32)
+        parts = self._out_parts(name, out, 3, "with want_points, out must be a (records, qpoints, points) triple") if want_points else (out, None, None)
+        rec, res = self._device_records(name, parts[0], n, (4,), parts[0] is None and count is not None)
+        qpts = self._device_out(name, parts[1], n, torch.float32, (3,), 0.0, count is not None) if want_points else None
+        pts = self._device_out(name, parts[2], n, torch.float32, (3,), 0.0, count is not None) if want_points else None
+        check(lib().rt_triangle_distance_device(self._h, C.c_void_p(tris.data_ptr()), stride, n, cnt, rad, slf, 0, C.c_void_p(rec.data_ptr()),
+                                                None if qpts is None else C.c_void_p(qpts.data_ptr()),
+                                                None if pts is None else C.c_void_p(pts.data_ptr()), self._stream_ptr(stream)))
+        return res + (qpts[:n], pts[:n]) if want_points else res
+
+    def triangle_within(self, tris, rmax=None, self_index=None, count=None, out=None, stream=None):
+        """rt_triangle_within_device: within[n] uint8, 1 where a candidate triangle is nearer to the query triangle than
+        its radius (where triangle_distance with the same arguments returns a triangle), else 0; the walk leaves a
+        query at the first such triangle. tris, rmax, self_index, count and stream as triangle_distance; out: a (>= n,)
+        uint8 tensor to write into. (No _device suffix, for triangle_distance's reason.)"""
+        import torch
+        name = "triangle_within"
+        n, stride = self._device_tris(name, tris)
+        cnt = self._device_count(name, count)
+        rad = self._device_vector(name, "rmax", rmax, n, torch.float32)
+        slf = self._device_vector(name, "self_index", self_index, n, torch.int32)
+        within = self._device_out(name, out, n, torch.uint8, (), 0, count is not None)
+        check(lib().rt_triangle_within_device(self._h, C.c_void_p(tris.data_ptr()), stride, n, cnt, rad, slf, 0,
+                                              C.c_void_p(within.data_ptr()), self._stream_ptr(stream)))
+        return within[:n]
+
     def closest_point(self, points, rmax=None):
         """rt_closest_point for numpy arrays: returns (triangle[n] int32, distance[n] float32, st[n, 2] float32,
         point[n, 3] float32), closest_point_device's bits. rmax: optional n search radii."""

@@ -200,4 +200,26 @@ inline const char *triangle_collides_args(bool scene, const void *d_qtris, int32
     return nullptr;
 }
 
+// The triangle entries' arrays, then the closest-point entry's rules for the record and the points.
+inline const char *triangle_distance_args(bool scene, const void *d_qtris, int32_t tri_stride, int32_t n, const void *d_count,
+                                          const void *d_rmax, const void *d_self, uint32_t flags, const void *d_hit_out,
+                                          const void *d_qpoint_out, const void *d_point_out) {
+    if (const char *m = check_arrays(kTriWords, scene, d_qtris, d_qtris, tri_stride, n)) return m;
+    if (n && !d_hit_out) return "output array is NULL";
+    if (misaligned(d_hit_out, sizeof(rt_hit))) return "d_hit_out must be 16-byte aligned";
+    if (misaligned(d_qpoint_out, 4) || misaligned(d_point_out, 4)) return "d_qpoint_out and d_point_out must be 4-byte aligned";
+    if (misaligned(d_count, 4) || misaligned(d_rmax, 4) || misaligned(d_self, 4)) return "d_count, d_rmax and d_self must be 4-byte aligned";
+    if (flags) return "flags must be 0";
+    return nullptr;
+}
+
+inline const char *triangle_within_args(bool scene, const void *d_qtris, int32_t tri_stride, int32_t n, const void *d_count,
+                                        const void *d_rmax, const void *d_self, uint32_t flags, const void *d_within_out) {
+    if (const char *m = check_arrays(kTriWords, scene, d_qtris, d_qtris, tri_stride, n)) return m;
+    if (n && !d_within_out) return "output array is NULL";
+    if (misaligned(d_count, 4) || misaligned(d_rmax, 4) || misaligned(d_self, 4)) return "d_count, d_rmax and d_self must be 4-byte aligned";
+    if (flags) return "flags must be 0";
+    return nullptr;
+}
+
 }  // namespace rt

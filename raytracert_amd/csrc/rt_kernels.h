@@ -273,6 +273,17 @@ void launch_tri_query(const DevScene &s, const float *xyz, const uint32_t *tri_v
 // rt_triangle_collides_device: collides[n] = 1 when a candidate overlaps the query triangle, else 0 (the any mode).
 void launch_tri_collides(const DevScene &s, const float *xyz, const uint32_t *tri_v, const void *qtris, int32_t tri_stride, int32_t n,
                          const int32_t *d_count, const int32_t *self, uint8_t *collides, hipStream_t stream);
+// Triangle-distance device query (rt_triangle_distance_device): per query triangle the rt_hit record of the candidate
+// triangle nearest to it (the lexicographic (dist2, index) minimum below rmax[i]^2; rmax null: no bound), with the
+// witness points on the query (qpoint) and on the scene (point), each 3n floats or null; self as launch_tri_query. The
+// tree walk (k_bvh_tri_dist) and the loop over every triangle (k_tri_dist) give the same bytes.
+void launch_tri_distance(const DevScene &s, const float *xyz, const uint32_t *tri_v, const void *qtris, int32_t tri_stride, int32_t n,
+                         const int32_t *d_count, const float *rmax, const int32_t *self, void *hit, float *qpoint, float *point,
+                         hipStream_t stream);
+// rt_triangle_within_device: within[n] = 1 when launch_tri_distance would return a triangle, else 0 (the walk leaves a
+// query at its first candidate below the bound).
+void launch_tri_within(const DevScene &s, const float *xyz, const uint32_t *tri_v, const void *qtris, int32_t tri_stride, int32_t n,
+                       const int32_t *d_count, const float *rmax, const int32_t *self, uint8_t *within, hipStream_t stream);
 // launch_gen_rays from the caller's device arrays in either layout (rt_trace_rays_device)
 void launch_gen_rays_device(const void *org, const void *dst, int32_t ray_stride, int32_t n, const DevWork &w,
                             hipStream_t stream);

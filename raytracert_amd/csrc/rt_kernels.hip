@@ -2654,8 +2654,8 @@ __device__ __forceinline__ bool make_qtri(V3 q0, V3 q1, V3 q2, QTri &t) {
     return !(nq[0] == 0.0 && nq[1] == 0.0 && nq[2] == 0.0);
 }
 
-// Whether triangle idx is a candidate, is not passed over for the query's self triangle, and overlaps the query.
-__device__ __forceinline__ bool tri_eval(const TriQuery &q, const TriRec *__restrict__ tris, int idx, const QTri &t) {
+// Whether triangle idx is a candidate and is not passed over for the query's self triangle; V: its vertices then.
+__device__ __forceinline__ bool tri_candidate(const TriQuery &q, const TriRec *__restrict__ tris, int idx, const QTri &t, float (&V)[3][3]) {
     const float4 nrec = reinterpret_cast<const float4 *>(tris + idx)[3];
     if (nrec.x == 0.0f && nrec.y == 0.0f && nrec.z == 0.0f) return false;
     const uint32_t *__restrict__ tv = q.tri_v + 3 * static_cast<size_t>(idx);
@@ -2667,7 +2667,17 @@ __device__ __forceinline__ bool tri_eval(const TriQuery &q, const TriRec *__rest
     const float *__restrict__ A = q.xyz + 3 * static_cast<size_t>(i0);
     const float *__restrict__ B = q.xyz + 3 * static_cast<size_t>(i1);
     const float *__restrict__ Cv = q.xyz + 3 * static_cast<size_t>(i2);
-    const float V[3][3] = {{A[0], A[1], A[2]}, {B[0], B[1], B[2]}, {Cv[0], Cv[1], Cv[2]}};
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        V[0][a] = A[a];
+        V[1][a] = B[a];
+        V[2][a] = Cv[a];
+    }
+    return true;
+}
+
+// Steps 1 to 4 of the header for the query t and a candidate's vertices V: whether the pair overlaps.
+__device__ __forceinline__ bool tri_pair_overlaps(const QTri &t, const float (&V)[3][3]) {
     const float lo[3] = {t.lo.x, t.lo.y, t.lo.z}, hi[3] = {t.hi.x, t.hi.y, t.hi.z};
     // 1: raw compares (most leaf triangles end here, before any binary64)
 #pragma unroll
@@ -2716,6 +2726,12 @@ __device__ __forceinline__ bool tri_eval(const TriQuery &q, const TriRec *__rest
         sep |= tri_axis(w, u, v);
     }
     return !sep;
+}
+
+// Whether triangle idx is a candidate, is not passed over for the query's self triangle, and overlaps the query.
+__device__ __forceinline__ bool tri_eval(const TriQuery &q, const TriRec *__restrict__ tris, int idx, const QTri &t) {
+    float V[3][3];
+    return tri_candidate(q, tris, idx, t, V) && tri_pair_overlaps(t, V);
 }
 
 struct TriLeaf {
@@ -2811,6 +2827,375 @@ __global__ __launch_bounds__(kBlock) void k_tri(const TriRec *__restrict__ tris,
     if (!active) return;
     if (kMode == kBoxAny) q.collides[j] = walk && found ? 1 : 0;
     else store_box<kMode>(bl, j, q);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Triangle-distance queries (rt_triangle_distance_device, rt_triangle_within_device): per query triangle the
+// candidate triangle nearest to it, as the lexicographic (dist2, index) minimum over the candidates with dist2 below
+// the query's bound, with the closest-point query's record and the two witness points, or (kTriDistWithin) only
+// whether there is one. Queries, candidates and the `self` pass-over are the overlap queries' (load_qtri,
+// tri_candidate). include/raytracert.h states the arithmetic; tri_feature_min and tri_pair_dist2 are that statement
+// op for op: binary64 on coordinates relative to the query's first vertex, the fifteen feature distances of the
+// pair in the header's order (query vertices against the candidate, candidate vertices against the query, the nine
+// edge pairs), and 0 instead of their minimum where tri_pair_overlaps says the pair overlaps.
+// The feature loops are rolled: three runtime passes that rotate the vertices of one triangle (moves, no indexed
+// registers) and a three by three nest for the edge pairs, so one closest_on_triangle64 per direction and one
+// closest_on_segments64 are live at a time (profiles/triangle_distance_kernel_resources.txt). The walk keeps dist2
+// and the index alone; the record's parameters and witnesses are evaluated once more for the winner (kFull), as
+// store_point does.
+//
+// Exactness (DESIGN.md §7 "Triangle-distance queries" has the argument in full). With d = 2^-53 and
+// M = scene_m1 + 2 max_j |Q_j|_1 every |u_j[a]| and |v_j[a]| is at most M. Every branch leaves its parameters in
+// [0, 1] (s + t <= 1 + d), so a computed witness lies within 11 d M per component of a point of its triangle, the
+// two witnesses are at least D - 27.8 d M apart for D the true distance of the triangles, and the rounding of
+// dot(r, r) takes at most 8.7 d M more: sqrt(dist2) >= D - 36.5 d M for a pair that tri_pair_overlaps does not
+// call overlapping. The boxes of the tree contain the vertices, so D is at least the distance Db between the
+// query's bounds and a child's box, and the computed box distance has sqrt(db2) <= Db (1 + 3 * 2^-24). A child is
+// skipped only when db2 exceeds
+//     cull2 = max(h h (1 + 1e-6), FLT_MIN),  h = (sqrtf(max((float)best2, FLT_MIN)) + 64 d M) (1 + 1e-6)
+// (tri_dist_cull; the factors cover the roundings of db2, of the conversion, of h and of the square; the two
+// FLT_MIN keep an underflow from shrinking the bound), which puts every candidate below it that does not overlap
+// at a dist2 strictly above best2. A candidate that overlaps is never below a skipped child: step 1 of the overlap
+// test did not separate it, so on every axis one of its vertices is at or below qhi and one at or above qlo, the
+// gap of any box that contains them is 0 and db2 is 0. So the result is the loop's over every triangle, ties by
+// index included (several overlapping candidates, all at 0, among them).
+// ---------------------------------------------------------------------------------------------
+enum { kTriDistClosest = 0, kTriDistWithin = 1 };
+
+struct TriDistQuery {
+    TriQuery base;              // xyz, tri_v, nt and self, as the overlap queries hold them (the rest unused)
+    const float *rmax;          // per query, or null
+    int4 *hit;                  // the records (kTriDistClosest)
+    float *qpoint, *point;      // the witnesses on the query and on the scene; each may be null
+    uint8_t *within;            // [n] (kTriDistWithin)
+};
+
+__device__ __forceinline__ double dot64(const double (&x)[3], const double (&y)[3]) { return (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]; }
+
+__device__ __forceinline__ double clamp01(double x) {
+    x = x < 0.0 ? 0.0 : x;
+    return x > 1.0 ? 1.0 : x;
+}
+
+// dot(a - b, a - b)
+__device__ __forceinline__ double dist2_64(const double (&a)[3], const double (&b)[3]) {
+    const double r[3] = {a[0] - b[0], a[1] - b[1], a[2] - b[2]};
+    return dot64(r, r);
+}
+
+// closest_on_triangle in binary64 on vertices: the point x = (a + s (b - a)) + t (c - a) of triangle a b c nearest to p.
+__device__ __forceinline__ void closest_on_triangle64(const double (&p)[3], const double (&a)[3], const double (&b)[3], const double (&c)[3],
+                                                      double &s, double &t, double (&x)[3]) {
+    const double ab[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]};
+    const double ac[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+    const double w[3] = {p[0] - a[0], p[1] - a[1], p[2] - a[2]};
+    const double d1 = dot64(ab, w), d2 = dot64(ac, w);
+    const double uu = dot64(ab, ab), uv = dot64(ab, ac), vv = dot64(ac, ac);
+    const double d3 = d1 - uu, d4 = d2 - uv;
+    const double d5 = d1 - uv, d6 = d2 - vv;
+    const double vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+    if (d1 <= 0.0 && d2 <= 0.0) {                                      // vertex 0
+        s = 0.0; t = 0.0;
+    } else if (d3 >= 0.0 && d4 <= d3) {                                // vertex 1
+        s = 1.0; t = 0.0;
+    } else if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {                  // edge 0-1
+        s = d1 / (d1 - d3); t = 0.0;
+    } else if (d6 >= 0.0 && d5 <= d6) {                                // vertex 2
+        s = 0.0; t = 1.0;
+    } else if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) {                  // edge 0-2
+        s = 0.0; t = d2 / (d2 - d6);
+    } else if (va <= 0.0 && d4 - d3 >= 0.0 && d5 - d6 >= 0.0) {        // edge 1-2
+        t = (d4 - d3) / ((d4 - d3) + (d5 - d6)); s = 1.0 - t;
+    } else {                                                           // interior, clamped by compares
+        const double q = 1.0 / ((va + vb) + vc);
+        s = vb * q; t = vc * q;
+        s = s < 0.0 ? 0.0 : s; s = s > 1.0 ? 1.0 : s;
+        const double m = 1.0 - s;
+        t = t < 0.0 ? 0.0 : t; t = t > m ? m : t;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) x[k] = (a[k] + s * ab[k]) + t * ac[k];
+}
+
+// The clamped closest points of the segments p0 p1 and r0 r1: x = p0 + sq (p1 - p0), y = r0 + tv (r1 - r0).
+// Parallel segments (a zero denominator) start from sq = 0.
+__device__ __forceinline__ void closest_on_segments64(const double (&p0)[3], const double (&p1)[3], const double (&r0)[3], const double (&r1)[3],
+                                                      double &sq, double &tv, double (&x)[3], double (&y)[3]) {
+    const double g[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
+    const double h[3] = {r1[0] - r0[0], r1[1] - r0[1], r1[2] - r0[2]};
+    const double r[3] = {p0[0] - r0[0], p0[1] - r0[1], p0[2] - r0[2]};
+    const double a = dot64(g, g), e = dot64(h, h), f = dot64(h, r), c = dot64(g, r), b = dot64(g, h);
+    const double den = a * e - b * b;
+    sq = den != 0.0 ? clamp01((b * f - c * e) / den) : 0.0;
+    tv = (b * sq + f) / e;
+    if (tv < 0.0) {
+        tv = 0.0;
+        sq = clamp01(-c / a);
+    } else if (tv > 1.0) {
+        tv = 1.0;
+        sq = clamp01((b - c) / a);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        x[k] = p0[k] + sq * g[k];
+        y[k] = r0[k] + tv * h[k];
+    }
+}
+
+// (x0, x1, x2) <- (x1, x2, x0): three of these restore x
+__device__ __forceinline__ void rotate3(double (&x)[3][3]) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double k = x[0][a];
+        x[0][a] = x[1][a];
+        x[1][a] = x[2][a];
+        x[2][a] = k;
+    }
+}
+
+// What the record needs of the feature minimum (kFull): which feature, its two parameters, the witnesses.
+struct TriFeature {
+    int f = 0;
+    double pa = 0.0, pb = 0.0;
+    double cq[3] = {0.0, 0.0, 0.0}, cv[3] = {0.0, 0.0, 0.0};
+};
+
+// The feature minimum of u (query) and v (candidate), both relative to Q_0: m = +inf, then each feature in order
+// takes over when its d2 < m. u and v come back as they were.
+template <bool kFull>
+__device__ __forceinline__ double tri_feature_min(double (&u)[3][3], double (&v)[3][3], TriFeature &w) {
+    double m = INFINITY;
+    auto take = [&](double d2, int f, double pa, double pb, const double (&cq)[3], const double (&cv)[3]) {
+        if (!(d2 < m)) return;
+        m = d2;
+        if (kFull) {
+            w.f = f;
+            w.pa = pa;
+            w.pb = pb;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                w.cq[a] = cq[a];
+                w.cv[a] = cv[a];
+            }
+        }
+    };
+#pragma unroll 1
+    for (int j = 0; j < 3; ++j) {   // features 0..2: Q_j against the candidate
+        double s, t, x[3];
+        closest_on_triangle64(u[0], v[0], v[1], v[2], s, t, x);
+        take(dist2_64(u[0], x), j, s, t, u[0], x);
+        rotate3(u);
+    }
+#pragma unroll 1
+    for (int j = 0; j < 3; ++j) {   // 3..5: V_j against the query
+        double s, t, x[3];
+        closest_on_triangle64(v[0], u[0], u[1], u[2], s, t, x);
+        take(dist2_64(x, v[0]), 3 + j, s, t, x, v[0]);
+        rotate3(v);
+    }
+#pragma unroll 1
+    for (int i = 0; i < 3; ++i) {   // 6 + 3 i + j: the query's edge Q_i Q_i+1 against the candidate's edge V_j V_j+1
+#pragma unroll 1
+        for (int j = 0; j < 3; ++j) {
+            double sq, tv, x[3], y[3];
+            closest_on_segments64(u[0], u[1], v[0], v[1], sq, tv, x, y);
+            take(dist2_64(x, y), 6 + 3 * i + j, sq, tv, x, y);
+            rotate3(v);
+        }
+        rotate3(u);
+    }
+    return m;
+}
+
+// u_j = Q_j - Q_0 and v_j = V_j - Q_0 in binary64 (the header's step 2)
+__device__ __forceinline__ void tri_relative(const QTri &t, const float (&V)[3][3], double (&u)[3][3], double (&v)[3][3]) {
+    const float Q[3][3] = {{t.q0.x, t.q0.y, t.q0.z}, {t.q1.x, t.q1.y, t.q1.z}, {t.q2.x, t.q2.y, t.q2.z}};
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            u[j][a] = static_cast<double>(Q[j][a]) - static_cast<double>(Q[0][a]);
+            v[j][a] = static_cast<double>(V[j][a]) - static_cast<double>(Q[0][a]);
+        }
+}
+
+// dist2 of the pair: 0 where it overlaps, else the feature minimum. The verdict comes first: most pairs of a walk
+// that reach here are either separated by its raw compares at once or overlap, and an overlapping pair needs no
+// feature.
+__device__ __forceinline__ double tri_pair_dist2(const QTri &t, const float (&V)[3][3]) {
+    if (tri_pair_overlaps(t, V)) return 0.0;
+    double u[3][3], v[3][3];
+    tri_relative(t, V, u, v);
+    TriFeature w;
+    return tri_feature_min<false>(u, v, w);
+}
+
+// One candidate against the best so far, as point_eval: the lexicographic (dist2, index) order once something is
+// found, dist2 < bound before (bidx < 0: best2 is the bound). true when best changed.
+__device__ __forceinline__ bool tri_dist_visit(const TriDistQuery &q, const TriRec *__restrict__ tris, int idx, const QTri &t, double &best2,
+                                               int &bidx) {
+    if (best2 == 0.0 && bidx >= 0 && idx > bidx) return false;   // nothing is below (0, bidx) at a greater index
+    float V[3][3];
+    if (!tri_candidate(q.base, tris, idx, t, V)) return false;
+    const double d2 = tri_pair_dist2(t, V);
+    if (d2 < best2 || (d2 == best2 && bidx >= 0 && idx < bidx)) {
+        best2 = d2;
+        bidx = idx;
+        return true;
+    }
+    return false;
+}
+
+// The query's triangle, its self triangle and its bound; false for an empty query or an empty search.
+template <int kStride>
+__device__ __forceinline__ bool load_qtri_bound(const void *__restrict__ qt, const TriDistQuery &q, int j, QTri &t, double &bound2) {
+    int after;
+    bool walk = load_qtri<kStride>(qt, q.base, j, t, after);
+    bound2 = INFINITY;
+    if (q.rmax) {
+        const float r = q.rmax[j];
+        walk = walk && r > 0.0f;
+        bound2 = static_cast<double>(r) * static_cast<double>(r);
+    }
+    return walk;
+}
+
+// The record and the witnesses of query j (bidx < 0: a miss), evaluated once more from the scene's arrays.
+__device__ __forceinline__ void store_tri_dist(const TriDistQuery &q, int j, int bidx, const QTri &t) {
+    int4 rec = make_int4(-1, as_int(INFINITY), 0, 0);
+    V3 cq = mk(0, 0, 0), cv = mk(0, 0, 0);
+    if (bidx >= 0) {
+        const uint32_t *__restrict__ tv = q.base.tri_v + 3 * static_cast<size_t>(bidx);
+        float V[3][3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float *__restrict__ P = q.base.xyz + 3 * static_cast<size_t>(tv[k]);
+            V[k][0] = P[0];
+            V[k][1] = P[1];
+            V[k][2] = P[2];
+        }
+        double u[3][3], v[3][3];
+        tri_relative(t, V, u, v);
+        TriFeature w;
+        const double m = tri_feature_min<true>(u, v, w);
+        const double d2 = tri_pair_overlaps(t, V) ? 0.0 : m;
+        // the candidate's barycentrics of c_V from the feature's parameters
+        double s = w.pa, tt = w.pb;                                          // 0..2: closest_on_triangle64's own
+        if (w.f >= 3 && w.f < 6) {                                           // 3..5: the vertex V_j
+            s = w.f == 4 ? 1.0 : 0.0;
+            tt = w.f == 5 ? 1.0 : 0.0;
+        } else if (w.f >= 6) {                                               // the edge V_j V_j+1 at tv
+            const int e = (w.f - 6) % 3;
+            s = e == 0 ? w.pb : e == 1 ? 1.0 - w.pb : 0.0;
+            tt = e == 0 ? 0.0 : e == 1 ? w.pb : 1.0 - w.pb;
+        }
+        rec = make_int4(bidx, as_int(sqrtf(static_cast<float>(d2))), as_int(static_cast<float>(s)), as_int(static_cast<float>(tt)));
+        cq = mk(static_cast<float>(static_cast<double>(t.q0.x) + w.cq[0]), static_cast<float>(static_cast<double>(t.q0.y) + w.cq[1]),
+                static_cast<float>(static_cast<double>(t.q0.z) + w.cq[2]));
+        cv = mk(static_cast<float>(static_cast<double>(t.q0.x) + w.cv[0]), static_cast<float>(static_cast<double>(t.q0.y) + w.cv[1]),
+                static_cast<float>(static_cast<double>(t.q0.z) + w.cv[2]));
+    }
+    q.hit[j] = rec;                                                                // one 16-byte store
+    if (q.qpoint) reinterpret_cast<V3 *>(q.qpoint)[j] = cq;
+    if (q.point) reinterpret_cast<V3 *>(q.point)[j] = cv;
+}
+
+// cull2 of the comment above; slack = 64 * 2^-53 * M
+__device__ __forceinline__ float tri_dist_cull(double best2, float slack) {
+    const float h = (sqrtf(fmaxf(static_cast<float>(best2), FLT_MIN)) + slack) * 1.000001f;
+    return fmaxf((h * h) * 1.000001f, FLT_MIN);
+}
+
+__device__ __forceinline__ float tri_dist_slack(const DevScene &sc, const QTri &t) {
+    const float q1 = fmaxf(fmaxf(fabsf(t.q0.x) + fabsf(t.q0.y) + fabsf(t.q0.z), fabsf(t.q1.x) + fabsf(t.q1.y) + fabsf(t.q1.z)),
+                           fabsf(t.q2.x) + fabsf(t.q2.y) + fabsf(t.q2.z));
+    return 64.0f * 1.1102230e-16f * (2.0f * q1 + sc.scene_m1);
+}
+
+// db2: the squared distance between the query's bounds and a child's box, bvh_walk's ordering key
+template <typename Box>
+__device__ __forceinline__ float box_box_dist2(const QTri &t, const Box &c) {
+    const float ex = fmaxf(fmaxf(c.lo(0) - t.hi.x, t.lo.x - c.hi(0)), 0.0f);
+    const float ey = fmaxf(fmaxf(c.lo(1) - t.hi.y, t.lo.y - c.hi(1)), 0.0f);
+    const float ez = fmaxf(fmaxf(c.lo(2) - t.hi.z, t.lo.z - c.hi(2)), 0.0f);
+    return (ex * ex + ey * ey) + ez * ez;
+}
+
+// kTriDistWithin: the walk leaves at the first candidate below the bound (bidx >= 0).
+template <int W, int kMode>
+__device__ __forceinline__ void bvh_tri_dist_walk(const DevScene &sc, const TriDistQuery &q, const QTri &t, bool walk, double &best2, int &bidx,
+                                                  const LaneStack &stack, unsigned &tests, unsigned &visits) {
+    // the always list: every lane (one whose query is empty takes nothing from it)
+    for (int i = 0; i < sc.n_always; ++i)
+        if (walk && !(kMode == kTriDistWithin && bidx >= 0)) tri_dist_visit(q, sc.tris, static_cast<int>(sc.always[i]), t, best2, bidx);
+    tests += static_cast<unsigned>(max(sc.n_always, 0));
+    if (!walk || (kMode == kTriDistWithin && bidx >= 0)) return;
+    const float slack = tri_dist_slack(sc, t);
+    float cull2 = tri_dist_cull(best2, slack);
+    bvh_walk<W, true>(
+        sc, stack, visits,
+        [&](const auto &c, float &db2) {
+            db2 = box_box_dist2(t, c);
+            return db2 <= cull2;
+        },
+        [&](int first, int cnt) {
+            bool better = false;
+            if (kMode == kTriDistWithin) {
+                for (int k = 0; k < cnt && bidx < 0; ++k) {
+                    tri_dist_visit(q, sc.tris, static_cast<int>(sc.leaf_idx[first + k]), t, best2, bidx);
+                    ++tests;
+                }
+                return bidx >= 0;
+            }
+            for (int k = 0; k < cnt; ++k) better |= tri_dist_visit(q, sc.tris, static_cast<int>(sc.leaf_idx[first + k]), t, best2, bidx);
+            tests += static_cast<unsigned>(cnt);
+            if (better) cull2 = tri_dist_cull(best2, slack);   // (only when the bound fell)
+            return false;
+        });
+}
+
+template <int W, int kStride, int kMode, bool kCount>
+__global__ __launch_bounds__(kBvhBlock) void k_bvh_tri_dist(const DevScene sc, const void *__restrict__ qt, int n,
+                                                            const int32_t *__restrict__ d_count, const TriDistQuery q) {
+    extern __shared__ int32_t lds_stack[];
+    const LaneStack stack = lane_stack(sc, lds_stack);
+    WorkTally<kCount> wt;
+    drive_queries(live_rays(d_count, n), 0, nullptr, [&](int j, int end) {
+        const bool active = j < end;
+        QTri t = no_qtri();
+        double best2 = INFINITY;
+        bool walk = false;
+        if (active) walk = load_qtri_bound<kStride>(qt, q, j, t, best2);
+        int bidx = -1;
+        wt.begin();
+        bvh_tri_dist_walk<W, kMode>(sc, q, t, walk, best2, bidx, stack, wt.tests, wt.visits);
+        wt.end();
+        if (!active) return;
+        if (kMode == kTriDistWithin) q.within[j] = bidx >= 0 ? 1 : 0;
+        else store_tri_dist(q, j, bidx, t);
+    });
+    wt.flush(sc.work);
+}
+
+// The same over every triangle in index order (RT_ACCEL_BRUTE_FORCE, or no tree could be built).
+template <int kStride, int kMode>
+__global__ __launch_bounds__(kBlock) void k_tri_dist(const TriRec *__restrict__ tris, int nt, const void *__restrict__ qt, int n,
+                                                     const int32_t *__restrict__ d_count, const TriDistQuery q) {
+    int j;
+    bool active;
+    if (!brute_lane(d_count, n, j, active)) return;
+    QTri t = no_qtri();
+    double best2 = INFINITY;
+    bool walk = false;
+    if (active) walk = load_qtri_bound<kStride>(qt, q, j, t, best2);
+    int bidx = -1;
+    for (int i = 0; i < nt; ++i) {
+        if (kMode == kTriDistWithin && (i & 15) == 0 && __all(!walk || bidx >= 0)) break;
+        if (walk && !(kMode == kTriDistWithin && bidx >= 0)) tri_dist_visit(q, tris, i, t, best2, bidx);
+    }
+    if (!active) return;
+    if (kMode == kTriDistWithin) q.within[j] = bidx >= 0 ? 1 : 0;
+    else store_tri_dist(q, j, bidx, t);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -5945,6 +6330,33 @@ void launch_tri_collides(const DevScene &s, const float *xyz, const uint32_t *tr
     if (n <= 0) return;
     const TriQuery q{xyz, tri_v, s.nt, nullptr, self, 0, nullptr, nullptr, collides};
     launch_tri_mode<kBoxAny>(s, qtris, tri_stride, n, d_count, q, stream);
+}
+
+namespace {
+template <int kMode>
+void launch_tri_dist_mode(const DevScene &s, const void *qtris, int32_t tri_stride, int32_t n, const int32_t *d_count, const TriDistQuery &q,
+                          hipStream_t stream) {
+    for_stride(tri_stride, [&](auto st) {
+        constexpr int kStride = st;
+        launch_query(s, n, 0, stream, [](auto w, auto c) { return k_bvh_tri_dist<w, kStride, kMode, c>; }, k_tri_dist<kStride, kMode>, qtris,
+                     n, d_count, q);
+    });
+}
+}  // namespace
+
+void launch_tri_distance(const DevScene &s, const float *xyz, const uint32_t *tri_v, const void *qtris, int32_t tri_stride, int32_t n,
+                         const int32_t *d_count, const float *rmax, const int32_t *self, void *hit, float *qpoint, float *point,
+                         hipStream_t stream) {
+    if (n <= 0) return;
+    const TriDistQuery q{{xyz, tri_v, s.nt, nullptr, self, 0, nullptr, nullptr, nullptr}, rmax, static_cast<int4 *>(hit), qpoint, point, nullptr};
+    launch_tri_dist_mode<kTriDistClosest>(s, qtris, tri_stride, n, d_count, q, stream);
+}
+
+void launch_tri_within(const DevScene &s, const float *xyz, const uint32_t *tri_v, const void *qtris, int32_t tri_stride, int32_t n,
+                       const int32_t *d_count, const float *rmax, const int32_t *self, uint8_t *within, hipStream_t stream) {
+    if (n <= 0) return;
+    const TriDistQuery q{{xyz, tri_v, s.nt, nullptr, self, 0, nullptr, nullptr, nullptr}, rmax, nullptr, nullptr, nullptr, within};
+    launch_tri_dist_mode<kTriDistWithin>(s, qtris, tri_stride, n, d_count, q, stream);
 }
 
 namespace {

@@ -15,6 +15,7 @@
 #                in-tree build; AB_PASSES; AB_WORKLOADS; AB_ARGS extra bench arguments): the timed loop only
 #   refit        tools/refit_probe.py: update / re-create / frame times of C4 and C5 under a deformation
 #   set_mesh     tools/set_mesh_probe.py: rt_scene_set_mesh against destroy + create, C4 and C5
+#   triangle_distance  tools/triangle_distance_probe.py: the triangle-distance queries on C4 (PROBE_SETS: displaced, self, random)
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"
 TAG=$1; shift
@@ -78,6 +79,9 @@ for STEP in "$@"; do
     set_mesh)
       timeout -k 10 500 python -u tools/set_mesh_probe.py profiles/set_mesh_probe.json > $TMPDIR/set_mesh_probe_$TAG.log 2>&1 || fail set_mesh $TMPDIR/set_mesh_probe_$TAG.log
       cat profiles/set_mesh_probe.json ;;
+    triangle_distance)
+      timeout -k 10 1000 python -u tools/triangle_distance_probe.py profiles/triangle_distance_probe.json ${PROBE_SETS:-} > $TMPDIR/triangle_distance_probe_$TAG.log 2>&1 || fail triangle_distance $TMPDIR/triangle_distance_probe_$TAG.log
+      cat profiles/triangle_distance_probe.json ;;
     *) echo "unknown step $STEP"; exit 2 ;;
   esac
 done
